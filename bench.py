@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- NMF multiplicative-update iterations/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|tiny] [--overlap 0|2|4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|tiny] [--overlap 0|2|4] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 (a plain `python bench.py --gpus N` with N > 1 starts that second command itself: self_launch)
 
@@ -11,11 +11,14 @@ that is already resident in HBM.  Default workload = the configuration the metri
 For N > 1, V and H are column-sharded over the ranks (total work fixed => "strong"), W is replicated, and
 each iteration has ONE all-reduce (RCCL) of the packed W-step partials.
 
-One JSON line on rank 0: metric/value/..., plus
+One JSON line on rank 0: metric/value/unit/higher_is_better/dtype/ms_per_step/...  A plain run sets up, warms up,
+times --steps steps and prints that line; nothing else.  --full adds what the headline figure does not need:
   roofline     dominant kernel: algorithmic flops per launch / mean launch duration (hipEvents on the stream the
                kernel runs on, recorded inside the timed region) against the fp32 MFMA peak (157.3 TFLOP/s)
   cpu_baseline the float64 literal restatement of nmf.m (oracle/, NumPy + OpenBLAS, all host cores) on a bounded
                column sample of the same workload, scaled linearly in n  (kind "port": MATLAB is unavailable)
+  N > 1        the all-reduce's share of a step, and rank 0's run of the whole problem alone (strong_scaling_eff)
+--dump-outputs DIR writes what the timed path returned after its last step (W, H, cost) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -54,6 +57,35 @@ WORKLOADS = {
 
 
 CPU_SAMPLE_COLS = {"c3": 4096, "c2": 8192, "c2is": 8192, "c2is256": 4096, "c2is512": 2048, "c4": 4096, "c4kl": 4096, "c4is": 4096, "tiny": 1024}
+
+DUMP_BYTES = 63 * 10 ** 6   # --dump-outputs: the arrays' data in all (64 MB with room for the .npy headers)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as <dirname>/<name>.npy (float32 stays float32, anything else becomes float64).  The smaller arrays are written whole;
+    one that does not fit in its share of DUMP_BYTES keeps a fixed sample of its rows (first axis: RandomState(DUMP_SEED), sorted), so that runs with the
+    same arguments write the same rows.  -> {name: shape, rows kept} for the result line"""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for k, v in arrays.items():
+        a = np.asarray(v)
+        arrs[k] = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+    left, info = DUMP_BYTES, {}
+    names = sorted(arrs, key=lambda k: arrs[k].nbytes)
+    for i, k in enumerate(names):
+        a = arrs[k]
+        d = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        share = left // (len(names) - i)
+        if a.nbytes > share and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, min(a.shape[0], share // (a.nbytes // a.shape[0])))
+            rows = np.sort(np.random.RandomState(DUMP_SEED).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            d["rows_kept"] = int(keep)
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+        info[k] = d
+    return info
 
 
 # what decides a launch's HBM traffic: the kernels, and the files that set grid / column-split geometry (the workgroup order over the XCDs decides L2 reuse)
@@ -159,7 +191,7 @@ def bench_nmfsc(args, torch, dist, dev, world, rank, force_dist):
     kw = dict(H_sparsity=args.h_sparsity, tolerance=-1.0, path=args.path)
     c0, info = nmfsc_sharded(V, W, H, maxiter=max(args.warmup, 1), **kw)
     sync()
-    _lib.check(lib.nmfx_nmfsc_profile(0 if args.no_profile else 1))
+    _lib.check(lib.nmfx_nmfsc_profile(1 if args.profile else 0))
     t0 = time.perf_counter()
     c1, info1 = nmfsc_sharded(V, W, H, maxiter=args.steps, resume=info, **kw)
     sync()
@@ -209,10 +241,13 @@ def bench_nmfsc(args, torch, dist, dev, world, rank, force_dist):
                        "line_search_tries_H": tries, "path": "fused kernels (objective = fused cost pass; dH = W'*(W*H - V) and the objective of the iterate from one fused residual pass; MU W step in Gram form)"},
             "effective_tflops": round((5.0 + float(np.mean(tries))) * f_mnk * world * its / 1e12, 3),
             "cost_first_last": [float(c1[0]), float(c1[-1])], "cost_monotone": bool(np.all(np.diff(c1) <= 0)),
-            "roofline": roof, "projfunc": pj,
             "world_size_seen": int(dist.get_world_size()) if (world > 1 or force_dist) else 1,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out.update(roofline=roof, projfunc=pj)
+        if args.dump_outputs:
+            out["outputs"] = dump_outputs(args.dump_outputs, dict(W=W.cpu().numpy(), H=H.cpu().numpy(), cost=np.asarray(c1, dtype=np.float64)))
+        if world == 1 and args.cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline_nmfsc(m, n, K, args.h_sparsity)
             except Exception as ex:
@@ -256,7 +291,7 @@ def bench_cnmfsc(args):
     lib = _lib.load()
     A.cnmfsc(V[:256, :512], 8, 2, dict(maxiter=1, H_sparsity=0.5))     # first-call costs
     total = args.warmup + args.steps
-    _lib.check(lib.nmfx_nmfsc_profile(0 if args.no_profile else 1))
+    _lib.check(lib.nmfx_nmfsc_profile(1 if args.profile else 0))
     info = {}
     W, H, c = A.cnmfsc(V, K, T, dict(W_init=W0, H_init=H0, H_sparsity=args.h_sparsity, maxiter=total, nmfx_disable_stop=True), info=info)
     nt = lib.nmfx_nmfsc_profile_ntags()
@@ -298,8 +333,12 @@ def bench_cnmfsc(args):
                       "name": args.workload, "m": m, "n": n, "K": K, "T": T, "divergence": "euclidean", "H_sparsity": args.h_sparsity, "line_search_tries_H": tries,
                       "timed_region": "outer iterations %d..%d of one blocking call, by the library's per-iteration completion times" % (args.warmup + 1, total)},
            "effective_tflops": round((12.0 + 2.0 * float(np.mean(tries[args.warmup:]))) * m * n * K * T * its / 1e12, 3),   # the REFERENCE's flop count per outer iteration (cnmfsc.m), not what the kernels issue
-           "cost_first_last": [float(c[0]), float(c[-1])], "roofline": roof}
-    if not args.no_cpu_baseline:
+           "cost_first_last": [float(c[0]), float(c[-1])]}
+    if args.full:
+        out["roofline"] = roof
+    if args.dump_outputs:
+        out["outputs"] = dump_outputs(args.dump_outputs, dict(W=W, H=H, cost=c))
+    if args.cpu_baseline:
         try:
             from oracle import nmf_oracle as O
             from threadpoolctl import threadpool_info
@@ -370,6 +409,8 @@ def bench_blocking(args):
                        allreduce_bytes=payload, allreduce_busbw_GBps=round(2.0 * (p_ - 1) / p_ * payload / max(ms.value * 1e-3, 1e-12) / 1e9, 2) if p_ > 1 else None,
                        rccl_library=(lib.nmfx_rccl_library(C.byref(ver)) or b"").decode(), rccl_version=ver.value,
                        note="one process, one host thread, one stream + engine per device (what a MEX caller of nmf() gets); ingest / iterate include the per-device uploads")
+        if args.dump_outputs:   # (one file set: with several backends the last one's)
+            out["outputs"] = dump_outputs(args.dump_outputs, dict(W=W, H=H, cost=c))
         print(json.dumps(out), flush=True)
 
 
@@ -398,8 +439,14 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="dev aid: no hipEvent pairs around the launch groups (the line then has no roofline object)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: hipEvent pairs around the launch groups inside the timed region (the roofline "
+                         "object), the CPU baseline, and for N > 1 the all-reduce time and rank 0's single-GPU run of the whole problem")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the timed path returned after its last step (W, H, cost) as DIR/<name>.npy, float32 / float64, "
+                         "64 MB at most in all (a larger array keeps a fixed, seeded sample of its rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the hipEvent pairs around the launch groups (the line then has no roofline object)")
     ap.add_argument("--path", type=int, default=0, help="0 auto, 1 generic (materialised V_hat), 2 fused")
     ap.add_argument("--overlap", type=int, default=int(os.environ.get("NMFX_W_CHUNKS", "0") or 0), choices=[0, 1, 2, 4, 8],
                     help="N > 1: row chunks of the W-step partial whose all-reduces overlap the next chunk's compute (0/1 = one blocking all-reduce)")
@@ -418,6 +465,8 @@ def main():
                          "the first ~0.1 s; a 20-step run of a 1.2 ms iteration read 7 %% low without it).  0 = off")
     ap.add_argument("--h-sparsity", type=float, default=0.5, help="c5: Hoyer sparseness target of the rows of H (nmfsc.m:102-110)")
     args = ap.parse_args()
+    args.profile = args.full and not args.no_profile
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
 
     if args.api == "blocking":
         return bench_blocking(args)
@@ -525,7 +574,7 @@ def main():
         spun_ms = (time.perf_counter() - t_sp) * 1e3
     eng.iterate(args.warmup, costs)
     sync()
-    eng.profile(0 if args.no_profile else 2)   # event pairs around the MFMA launch groups only: bracketing the small kernels too costs 0.4 % at N = 1, 4 % on an 8-GPU shard
+    eng.profile(2 if args.profile else 0)   # event pairs around the MFMA launch groups only: bracketing the small kernels too costs 0.4 % at N = 1, 4 % on an 8-GPU shard
     t0 = time.perf_counter()
     eng.iterate(args.steps, costs[args.warmup:])
     sync()
@@ -549,7 +598,10 @@ def main():
     # N > 1: rank 0 also times the WHOLE problem on its own GPU (no collective) right after the timed region, so the line carries
     # its own strong-scaling reference; the driver computes efficiency itself from the per-N lines, this is a cross-check
     single_its = None
-    if world > 1 and rank == 0 and alg == "nmf" and (m * n * 4 + 3 * m * K * 4 * 4 + 3 * n * K * 4) < 40e9:
+    outputs = None
+    if args.dump_outputs and rank == 0:   # what a caller of the engine holds after the last timed step: its W, its own columns of H, the global costs
+        outputs = dump_outputs(args.dump_outputs, dict(W=eng.W.cpu().numpy(), H=eng.H_local.cpu().numpy(), cost=c[args.warmup:]))
+    if args.full and world > 1 and rank == 0 and alg == "nmf" and (m * n * 4 + 3 * m * K * 4 * 4 + 3 * n * K * 4) < 40e9:
         try:
             del eng
             torch.cuda.empty_cache()
@@ -617,8 +669,9 @@ def main():
                                 0: "generic GEMM (materialised V_hat)"}[path_kind]},
             "effective_tflops": round(f_alg * its / 1e12, 3),
             "cost_first_last": [float(c[0]), float(c[-1])], "cost_monotone": bool(np.all(np.diff(c) <= 1e-7 * abs(c[0]))),
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roof
         out["data"] = "synthetic (numpy RandomState 1000 / 1 / 2, SURVEY 8(d))" if args.numpy_inputs else "synthetic"
         if args.numpy_inputs:
             # the run's costs against the float64 oracle's at this geometry (tests/golden/fullsize_*.npz, made by tests/golden/make_fullsize_golden.py; read only --
@@ -655,7 +708,9 @@ def main():
         if single_its is not None:
             out["single_gpu_its_same_run"] = round(single_its, 4)
             out["strong_scaling_eff"] = round(its / (world * single_its), 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if outputs is not None:
+            out["outputs"] = outputs
+        if world == 1 and args.cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(alg, div, m, n, K, T, args.workload)
             except Exception as ex:  # the baseline must never take the GPU number down with it

@@ -2,7 +2,7 @@
 # Everything the FIRST lease of an 8-GPU MI355X node should produce, in one shot (no scaling curve has ever been measured -- this pool has
 # 1-GPU boxes -- so the first contact must be self-describing, not a debug session).   bash scripts/first_8gpu_lease.sh [outdir]     (~6 min)
 #
-# Every line is bench.py's JSON line; for N > 1 it carries world_size_seen, per_rank_ms_per_step, all_ranks_same_path, allreduce_ms_per_step,
+# Every line is bench.py's JSON line (with --full); for N > 1 it carries world_size_seen, per_rank_ms_per_step, all_ranks_same_path, allreduce_ms_per_step,
 # allreduce_busbw_GBps (+ the one-link 153 GB/s and seven-link 1071 GB/s bounds), single_gpu_its_same_run and strong_scaling_eff = value / (N * single).
 #   1. the headline (c3: nmf KL 16384 x 65536, K = 256) at N = 1, 2, 4, 8 over RCCL (one process per GPU, torch.distributed nccl)   -> the scaling curve
 #   2. N = 8 with the row-chunked W step overlapping the all-reduce: --overlap 2, 4                                                  -> is overlap worth it on xGMI?
@@ -25,7 +25,7 @@ try:
 except Exception as e: print('$2: no JSON line (%s)' % e)"; }
 run() { # run <name> <bench args...>
   name=$1; shift
-  timeout 600 python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "rc $?" >> $OUT/$name.err; line $OUT/$name.json $name; }
+  timeout 600 python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "rc $?" >> $OUT/$name.err; line $OUT/$name.json $name; }
 for N in 1 2 4 8; do [ $N -le $NG ] && run c3_n$N --gpus $N --steps 20 --warmup 5 --no-cpu-baseline; done
 if [ $NG -ge 8 ]; then
   for C in 2 4; do run c3_n8_overlap$C --gpus 8 --steps 20 --warmup 5 --no-cpu-baseline --overlap $C; done

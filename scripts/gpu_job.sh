@@ -6,9 +6,9 @@
 # steps (run in the order given; a variant is an A/B build of the kernel switches, nmf_toolbox_amd/build.py --variant):
 #   ubench[:tiles]                  scripts/ubench_mfma (the fused kernel's MFMA / LDS / VALU skeleton)            -> <tag>_ubench.jsonl
 #   tests[:pytest args]             python -m pytest tests -m gpu -q <args>                                        -> <tag>_gputests.log, <tag>_parity_errors.json
-#   bench:<workload>[:variant[:extra bench.py args]]   the driver's line (--steps 20 --warmup 5, CPU baseline only for the default library)
+#   bench:<workload>[:variant[:extra bench.py args]]   the driver's line with --full (--steps 20 --warmup 5, CPU baseline only for the default library)
 #                                                                                                                  -> <tag>_bench_<workload>[_<variant>].json
-#   steady:<workload>[:variant]     --steps 200 --no-cpu-baseline                                                  -> <tag>_bench_<workload>[_<variant>]_steady.json
+#   steady:<workload>[:variant]     --steps 200 --full --no-cpu-baseline                                            -> <tag>_bench_<workload>[_<variant>]_steady.json
 #   prof:<workload>[:variant]       rocprofv3 --kernel-trace --stats of the bench command                          -> <tag>_<workload>[_<variant>]_kernel_stats.md
 #   pmc:<workload>[:variant]        the three separate --pmc passes (scripts/pmc_passes.sh)                        -> <tag>_<workload>_pmc.md
 #   campaign:<script>:<seed>:<seconds>[:args]   scripts/<script>.py in the BACKGROUND (joined at the end)          -> <tag>_<script>_<seed>.log
@@ -31,7 +31,7 @@ for step in "$@"; do
       tail -14 gpurun_out/${TAG}_gputests.log | cut -c1-220 ;;
     bench|steady)
       sfx=""; [ -n "$b" ] && sfx="_$b"
-      if [ $kind = steady ]; then args="--steps 200 --warmup 5 --no-cpu-baseline"; sfx="${sfx}_steady"; else args="--steps 20 --warmup 5"; [ -n "$b" ] && args="$args --no-cpu-baseline"; fi
+      if [ $kind = steady ]; then args="--steps 200 --warmup 5 --full --no-cpu-baseline"; sfx="${sfx}_steady"; else args="--steps 20 --warmup 5 --full"; [ -n "$b" ] && args="$args --no-cpu-baseline"; fi
       NMFX_LIB_VARIANT=$b python bench.py --workload $a $args $c > gpurun_out/${TAG}_bench_${a}${sfx}.json 2> gpurun_out/${TAG}_bench_${a}${sfx}.err
       tail -1 gpurun_out/${TAG}_bench_${a}${sfx}.json | python -c "
 import json,sys

@@ -136,6 +136,27 @@ def test_pmc_traffic_stamp_guards_the_bench_line():
         assert got == {} and "STALE" in note and "withheld" in note
 
 
+def test_bench_dump_outputs_stays_in_budget_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 stays float32, the rest is float64; small arrays are written whole, one past its share of the 64 MB keeps a fixed,
+    seeded sample of its rows -- the same rows in every run, so two builds can be compared file for file"""
+    sys.path.insert(0, ROOT)
+    import bench
+    W = np.arange(256 * 16384, dtype=np.float32).reshape(256, 16384)           # the c3 shapes: W 16 MB, H 64 MB
+    H = np.arange(65536 * 256, dtype=np.float32).reshape(65536, 256)
+    cost = np.linspace(2.0, 1.0, 20)
+    infos = []
+    for d in ("a", "b"):
+        infos.append(bench.dump_outputs(str(tmp_path / d), dict(W=W, H=H, cost=cost.astype(np.float32).astype(np.float16))))
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("W", "H", "cost")}
+    assert infos[0] == infos[1] and "rows_kept" in infos[0]["H"] and "rows_kept" not in infos[0]["W"]
+    assert got["W"].dtype == np.float32 and got["H"].dtype == np.float32 and got["cost"].dtype == np.float64
+    assert np.array_equal(got["W"], W) and got["cost"].shape == (20,)
+    assert sum(os.path.getsize(str(tmp_path / "a" / (k + ".npy"))) for k in got) <= 64 * 10 ** 6
+    rows = got["H"][:, 0] / 256                                                   # each row of H carries its own index
+    assert len(rows) == infos[0]["H"]["rows_kept"] > 65536 // 4 and np.all(np.diff(rows) > 0) and np.array_equal(got["H"], H[rows.astype(np.int64)])
+    assert np.array_equal(np.load(str(tmp_path / "b" / "H.npy")), got["H"])
+
+
 def test_abi_version_and_sizes_are_checked_by_the_loaders():
     """nmfx_problem grew (multi_backend) -- a client built against another header must be turned away, not read past its struct"""
     L = _lib()

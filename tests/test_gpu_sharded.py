@@ -875,6 +875,35 @@ def test_bench_self_launches_two_ranks(gpu_lib, workload):
     assert out["cost_monotone"] and len(out["per_rank_ms_per_step"]["all"]) == 2
 
 
+def test_bench_plain_line_full_line_and_dumped_outputs(gpu_lib, tmp_path):
+    """A plain `bench.py` run prints the headline line only (no roofline, no CPU baseline); --full adds the roofline; --dump-outputs writes what the timed
+    path returned after its last step (W, H, the timed steps' costs), identical between two runs of the same arguments up to rounding."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    lines = []
+    for extra in (["--dump-outputs", str(tmp_path / "a")], ["--dump-outputs", str(tmp_path / "b")], ["--full", "--no-cpu-baseline"]):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny"] + extra,
+                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        got = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(got) == 1, r.stdout
+        lines.append(json.loads(got[0]))
+    for out in lines:
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f32" and out["higher_is_better"] is True
+        assert out["unit"] == "iterations/s" and abs(out["ms_per_step"] * out["value"] - 1e3) < 5e-2 * 1e3
+        assert "cpu_baseline" not in out
+    assert "roofline" not in lines[0] and "roofline" in lines[2] and "outputs" not in lines[2]
+    assert lines[2]["roofline"] is None or lines[2]["roofline"]["launches"] >= 3
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("W", "H", "cost")}
+    b = {k: np.load(str(tmp_path / "b" / (k + ".npy"))) for k in ("W", "H", "cost")}
+    assert a["W"].shape == (16, 512) and a["H"].shape == (1024, 16) and a["cost"].shape == (3,) and a["cost"].dtype == np.float64
+    assert np.isclose(a["cost"][-1], lines[0]["cost_first_last"][1], rtol=1e-12)
+    assert rel_fro(a["W"], b["W"]) < 1e-5 and rel_fro(a["H"], b["H"]) < 1e-5 and rel_fro(a["cost"], b["cost"]) < 1e-6
+
+
 @pytest.mark.parametrize("div,K", [("euclidean", 64), ("is", 256)])
 def test_engine_without_the_transposed_copy_of_V(gpu_lib, div, K):
     """nmfx_engine_desc.flags bit 0 / Engine(no_vt=True): the euclidean fused path -- and IS above K = 192, whose H step otherwise runs as 4 + 2 m*n*K on that copy --
