@@ -166,6 +166,20 @@ nmfx_status nmfx_reconstruct(int64_t m, int64_t n, int32_t K, int32_t T, int32_t
  * be NULL; order_out (optional, [K]) receives the 0-based column permutation. */
 nmfx_status nmfx_sort_dictionary(int64_t m, int32_t K, int64_t n, int32_t dtype, const void *W, const void *H,
                                  void *W_sorted, void *H_sorted, int32_t *order_out, int32_t device);
+/* [W,H,P,cost] = cmfwisa(V, num_basis_elems, config)  -- replaces cmfwisa.m:1 (hot loop cmfwisa.m:175-224).  A new entry point; no structure
+ * grows and no existing entry point changes, so NMFX_VERSION stays 600.
+ *   p->V       real part of V (m x n, p->dtype); V_imag its imaginary part, or NULL for a real V
+ *   P_init_re / P_init_im   m x n x num_sources initial phases (source index slowest); P_init_re == NULL selects exp(1j*angle(V)) for every source,
+ *              formed on the device (cmfwisa.m:119, angle(0) = 0); P_init_im == NULL: real phases
+ *   P_fixed    [num_sources] or NULL = all false (cmfwisa.m:131-150)
+ *   P_re / P_im  out: m x n x num_sources, p->dtype
+ * K_s, num_sources, H_sparsity, W_fixed, H_fixed, maxiter, tolerance (< 0 disables the stop rule), device and path mean what they mean for nmfx_nmf;
+ * W_init / H_init are required (the random defaults stay in the wrapper), W_init is normalised to unit L2 columns even when W_fixed is set
+ * (cmfwisa.m:153-155).  divergence, alpha, beta and W_sparsity are ignored (the reference validates and never uses them).  T must be 1 and n_gpus <= 1
+ * (NMFX_ERR_UNSUPPORTED otherwise).  result.cost needs maxiter entries and is trimmed by the stop rule like nmf's.  nmfx_last_call_timing describes it. */
+nmfx_status nmfx_cmfwisa(const nmfx_problem *p, const void *V_imag,
+                         const void *P_init_re, const void *P_init_im, const uint8_t *P_fixed,
+                         nmfx_result *r, void *P_re, void *P_im);
 /* [v,usediters] = projfunc(s, k1, k2, nn) applied to `count` vectors of length N (stride N) -- replaces projfunc.m:1 */
 nmfx_status nmfx_projfunc(int64_t N, int32_t count, int32_t dtype, const void *s, double k1, double k2,
                           int32_t nn, void *v, int32_t *usediters, int32_t device);
@@ -184,7 +198,7 @@ nmfx_status nmfx_minmax_dev(void *stream, const float *X_dev, int64_t count, dou
 nmfx_status nmfx_scale_dev(void *stream, const float *X_dev, int64_t count, double divide_by, float *out_dev);
 
 /* Measurement hook for the blocking calls (bench.py --api blocking): wall seconds the last nmfx_nmf / nmfx_cnmf / nmfx_lnmf /
- * nmfx_constrainednmf on the calling thread spent moving the host arrays in (host-side fp64 -> fp32 conversion on threads + DMA through
+ * nmfx_constrainednmf / nmfx_cmfwisa on the calling thread spent moving the host arrays in (host-side fp64 -> fp32 conversion on threads + DMA through
  * two pinned buffers), iterating, and moving the results out; and the bytes of host arrays read / written.  Any pointer may be NULL. */
 nmfx_status nmfx_last_call_timing(double *ingest_s, double *iterate_s, double *egress_s, double *host_bytes_in, double *host_bytes_out);
 

@@ -9,6 +9,7 @@
     W, H, cost = cnmfsc(V, num_basis_elems, context_len, config)  cnmfsc.m:1          (f1)
     W, H, Z, A, cost = constrainednmf(V, labels, num_basis_elems, config)  constrainednmf.m:1   (f4)
     W_sorted, H_sorted = SortDictionary(W, H)                     SortDictionary.m:1  (f4)
+    W, H, P, cost = cmfwisa(V, num_basis_elems, config)           cmfwisa.m:1         (complex V, per-source phases)
 
 Same argument meaning, defaults and error behaviour as the MATLAB functions (a MATLAB cell array is
 a Python list, a struct a dict; errors are ValueError carrying the reference's message).  This file
@@ -515,6 +516,102 @@ def cnmfsc(V, num_basis_elems, context_len, config=None, device=0, info=None):
                     converged_early=bool(r.converged_early))
     Wr = np.array(Wout)
     return (Wr[:, :, 0] if T == 1 else Wr), np.array(Hout), cost[: r.cost_len].copy()
+
+
+def cmfwisa(V, num_basis_elems, config=None, device=0):
+    """[W, H, P, cost] = cmfwisa(V, num_basis_elems, config)  -- cmfwisa.m:1 (complex NMF with intra-source additivity).
+
+    V may be real or complex: float32 / complex64 run in single precision and the outputs keep it, anything else runs as float64 /
+    complex128.  The shared ValidateParameters.m branches for 'cmfwisa' are those of nmf (random defaults max(rand, eps), W column-normalised);
+    the phase arguments follow cmfwisa.m:110-150 and P comes back as a list when there are several sources or P_init was a list.
+    Extensions: seed / rng, nmfx_path (0 auto, 1 generic passes, 2 require the fused E pass), nmfx_disable_stop.
+
+    Reference behaviour kept as it is:
+      - W_sparsity is validated and never used (cmfwisa.m has no W penalty);
+      - divergence, alpha and beta are accepted and ignored (the cost is always sum(abs(V - V_hat).^2) + lambda terms, no 0.5);
+      - W_init is normalised to unit L2 columns even when W_fixed is set (cmfwisa.m:153-155);
+      - a P_init list of the wrong length raises "Requested I encoding matrices. Given J initial phase matrices." (cmfwisa.m:122);
+      - a P_fixed list of the wrong length raises "Requested I basis matrices. Given J update switches." (cmfwisa.m:138);
+      - a P_init that is not a list with more than one source is an index error in MATLAB: a ValueError here.
+    """
+    V = np.asarray(V)
+    if V.ndim != 2:
+        raise ValueError("V must be a matrix")
+    single = V.dtype in (np.float32, np.complex64)
+    rdt = np.float32 if single else np.float64
+    m, n = V.shape
+    Ks = [int(k) for k in (num_basis_elems if _is_cell(num_basis_elems) else [num_basis_elems])]   # cmfwisa.m:104-107
+    S = len(Ks)
+    cfg, W, H, is_W_cell, is_H_cell = _validate(V, Ks, 1, config, False)                           # cmfwisa.m:108
+    Pi = cfg.get("P_init", None)                                                                   # cmfwisa.m:110-129
+    if _isempty(Pi):
+        is_P_cell, P = S != 1, None
+    elif _is_cell(Pi) and len(Pi) != S:
+        raise ValueError("Requested %d encoding matrices. Given %d initial phase matrices." % (S, len(Pi)))
+    elif not _is_cell(Pi):
+        if S != 1:
+            raise ValueError("P_init must be a list of %d phase matrices when there are %d sources" % (S, S))
+        is_P_cell, P = False, [np.asarray(Pi)]
+    else:
+        is_P_cell, P = True, [np.asarray(x) for x in Pi]
+    Pf = cfg.get("P_fixed", None)                                                                  # cmfwisa.m:131-150
+    if _isempty(Pf):
+        P_fixed = [False] * S
+    elif _is_cell(Pf) and len(Pf) > 1 and len(Pf) != S:
+        raise ValueError("Requested %d basis matrices. Given %d update switches." % (S, len(Pf)))
+    elif not _is_cell(Pf) or len(Pf) == 1:
+        P_fixed = [bool(Pf[0] if _is_cell(Pf) else Pf)] * S
+    else:
+        P_fixed = [bool(x) for x in Pf]
+    for s in range(S):
+        if W[s].shape != (m, Ks[s]):
+            raise ValueError("W_init{%d} must be %d-by-%d" % (s + 1, m, Ks[s]))
+        if H[s].shape != (Ks[s], n):
+            raise ValueError("H_init{%d} must be %d-by-%d" % (s + 1, Ks[s], n))
+        if P is not None and P[s].shape != (m, n):
+            raise ValueError("P_init{%d} must be %d-by-%d" % (s + 1, m, n))
+    K = int(sum(Ks))
+    Vr = _f_order(np.real(V), rdt)
+    Vi = _f_order(np.imag(V), rdt) if np.iscomplexobj(V) else None
+    W_all = _f_order(np.concatenate(W, axis=1), rdt)
+    H_all = _f_order(np.concatenate(H, axis=0), rdt)
+    Pr0 = Pi0 = None
+    if P is not None:
+        Pr0 = np.asfortranarray(np.stack([np.real(x) for x in P], axis=2), dtype=rdt)
+        Pi0 = np.asfortranarray(np.stack([np.imag(x) if np.iscomplexobj(x) else np.zeros(x.shape) for x in P], axis=2), dtype=rdt)
+    maxiter = int(cfg["maxiter"])
+    Wout = np.zeros((m, K), order="F", dtype=rdt)
+    Hout = np.zeros((K, n), order="F", dtype=rdt)
+    Pre = np.zeros((m, n, S), order="F", dtype=rdt)
+    Pim = np.zeros((m, n, S), order="F", dtype=rdt)
+    cost = np.zeros(maxiter)
+    Ks_a = np.asarray(Ks, dtype=np.int32)
+    lh = np.asarray(cfg["H_sparsity"], dtype=np.float64)
+    fw = np.asarray(cfg["W_fixed"], dtype=np.uint8)
+    fh = np.asarray(cfg["H_fixed"], dtype=np.uint8)
+    fp = np.asarray(P_fixed, dtype=np.uint8)
+    p = _lib.Problem()
+    p.m, p.n, p.K_total, p.T, p.dtype = m, n, K, 1, (_lib.F32 if single else _lib.F64)
+    p.V, p.W_init, p.H_init = _fptr(Vr), _fptr(W_all), _fptr(H_all)
+    p.divergence, p.alpha, p.beta = _lib.DIV_EUCLIDEAN, 1.0, 1.0
+    p.num_sources, p.K_s = S, _fptr(Ks_a)
+    p.H_sparsity, p.W_fixed, p.H_fixed = _fptr(lh), _fptr(fw), _fptr(fh)
+    p.maxiter = maxiter
+    p.tolerance = -1.0 if cfg.get("nmfx_disable_stop", False) else float(cfg["tolerance"])
+    p.device = int(device)
+    p.path = int(cfg.get("nmfx_path", 0))
+    r = _lib.Result()
+    r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
+    _lib.check(_lib.load().nmfx_cmfwisa(C.byref(p), _fptr(Vi) if Vi is not None else None, _fptr(Pr0) if Pr0 is not None else None,
+                                        _fptr(Pi0) if Pi0 is not None else None, _fptr(fp), C.byref(r), _fptr(Pre), _fptr(Pim)))
+    cost = cost[: r.cost_len].copy()
+    Wl, Hl, k0 = [], [], 0
+    for s in range(S):
+        Wl.append(np.array(Wout[:, k0:k0 + Ks[s]]))
+        Hl.append(np.array(Hout[k0:k0 + Ks[s], :]))
+        k0 += Ks[s]
+    Pl = [Pre[:, :, s] + 1j * Pim[:, :, s] for s in range(S)]
+    return (Wl if is_W_cell else Wl[0]), (Hl if is_H_cell else Hl[0]), (Pl if is_P_cell else Pl[0]), cost   # cmfwisa.m:227-237
 
 
 def ReconstructFromDecomposition(W, H, device=0):
