@@ -180,6 +180,20 @@ nmfx_status nmfx_sort_dictionary(int64_t m, int32_t K, int64_t n, int32_t dtype,
 nmfx_status nmfx_cmfwisa(const nmfx_problem *p, const void *V_imag,
                          const void *P_init_re, const void *P_init_im, const uint8_t *P_fixed,
                          nmfx_result *r, void *P_re, void *P_im);
+/* [W,H,cost] = seminmf(V, num_basis_elems, config)  -- replaces seminmf.m:1 (hot loop seminmf.m:65-89).  A new entry point; no structure grows, so
+ * NMFX_VERSION stays 600.  V may have mixed sign.  Fields used: m, n, K_total, T (must be 1), dtype, V, W_init, H_init (both required: the default
+ * H_init comes from nmfx_kmeans in the wrapper), num_sources (must be 1), W_fixed[0], H_fixed[0], maxiter, tolerance (< 0 disables the stop rule),
+ * device and path (0 auto, 1 generic passes, 2 require the fused H pass: K_total <= 256, m and n >= 64).  divergence, alpha, beta and the
+ * sparsities are ignored.  n_gpus > 1 is NMFX_ERR_UNSUPPORTED.  K_total > n is NMFX_ERR_INVALID (H*H' is singular by construction), and so is an
+ * H*H' whose Cholesky factor meets a pivot <= 0 or not finite (the message names the iteration; MATLAB warns and goes on with Inf / NaN).
+ * W is never column-normalised.  result.cost needs maxiter entries and is trimmed by the stop rule like nmf's.  nmfx_last_call_timing describes it. */
+nmfx_status nmfx_seminmf(const nmfx_problem *p, nmfx_result *r);
+/* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
+ * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
+ * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,
+ * dtype) and iters_out may be NULL.  n < k, or fewer distinct points than clusters, is NMFX_ERR_INVALID. */
+nmfx_status nmfx_kmeans(int64_t m, int64_t n, int32_t k, int32_t dtype, const void *X, const double *u, int32_t maxiter,
+                        int32_t *idx_out, void *centroids_out, int32_t *iters_out, int32_t device);
 /* [v,usediters] = projfunc(s, k1, k2, nn) applied to `count` vectors of length N (stride N) -- replaces projfunc.m:1 */
 nmfx_status nmfx_projfunc(int64_t N, int32_t count, int32_t dtype, const void *s, double k1, double k2,
                           int32_t nn, void *v, int32_t *usediters, int32_t device);

@@ -10,6 +10,7 @@
     W, H, Z, A, cost = constrainednmf(V, labels, num_basis_elems, config)  constrainednmf.m:1   (f4)
     W_sorted, H_sorted = SortDictionary(W, H)                     SortDictionary.m:1  (f4)
     W, H, P, cost = cmfwisa(V, num_basis_elems, config)           cmfwisa.m:1         (complex V, per-source phases)
+    W, H, cost = seminmf(V, num_basis_elems, config)              seminmf.m:1         (mixed-sign V, k-means default H_init)
 
 Same argument meaning, defaults and error behaviour as the MATLAB functions (a MATLAB cell array is
 a Python list, a struct a dict; errors are ValueError carrying the reference's message).  This file
@@ -612,6 +613,99 @@ def cmfwisa(V, num_basis_elems, config=None, device=0):
         k0 += Ks[s]
     Pl = [Pre[:, :, s] + 1j * Pim[:, :, s] for s in range(S)]
     return (Wl if is_W_cell else Wl[0]), (Hl if is_H_cell else Hl[0]), (Pl if is_P_cell else Pl[0]), cost   # cmfwisa.m:227-237
+
+
+def _kmeans(X, k, u, maxiter=100, device=0):
+    """labels (0-based int32), centroids (m x k) and Lloyd iterations of the deterministic k-means on the columns of X (nmfx_kmeans; device only)"""
+    X = _as_data(X)
+    m, n = X.shape
+    X = _f_order(X, X.dtype)
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    idx = np.zeros(n, dtype=np.int32)
+    cen = np.zeros((m, k), order="F", dtype=X.dtype)
+    iters = C.c_int32(0)
+    _lib.check(_lib.load().nmfx_kmeans(m, n, int(k), _lib.F32 if X.dtype == np.float32 else _lib.F64, _fptr(X), _fptr(u), int(maxiter), _fptr(idx),
+                                       _fptr(cen), C.byref(iters), int(device)))
+    return idx, cen, int(iters.value)
+
+
+def seminmf(V, num_basis_elems, config=None, device=0):
+    """[W, H, cost] = seminmf(V, num_basis_elems, config)  -- seminmf.m:1 (semi-NMF: V of mixed sign, W of mixed sign, H >= 0).
+
+    The local ValidateParameters (seminmf.m:99-144), in its order: H_init defaults to kmeans(V.', K) as an indicator matrix plus 0.2 (the k-means
+    uniforms are the first draws of the RNG), W_init to 2*rand(m, K) - 1 (the second), W_fixed / H_fixed to false, maxiter <= 0 to 100 and
+    tolerance <= 0 to 1e-3.  W is never column-normalised (seminmf.m:92-94 is commented out).  float32 V runs in single precision and returns
+    float32; anything else runs as float64.  Extensions: seed / rng, nmfx_path (0 auto, 1 generic passes, 2 require the fused H pass),
+    nmfx_disable_stop.
+
+    The default H_init runs the library's deterministic k-means (nmfx_kmeans, on the device): k-means++ seeding from k host uniforms, batch Lloyd
+    updates, squared Euclidean distance, the 'singleton' empty-cluster rule; tests/seminmf_oracle.py restates it.  MATLAB's random stream is not
+    reproduced.
+
+    Deliberate deviations from seminmf.m:
+      - an H*H' that is not positive definite (an all-zero row of H, for one) raises NmfxError naming the iteration; MATLAB warns "singular to
+        working precision" and goes on with Inf / NaN;
+      - num_basis_elems > size(V, 2) is refused up front (H*H' is singular by construction);
+      - a list for num_basis_elems (several sources) is a ValueError; in MATLAB it fails inside ValidateParameters.
+    """
+    V = _as_data(V)
+    if V.ndim != 2:
+        raise ValueError("V must be a matrix")
+    if _is_cell(num_basis_elems) or np.ndim(num_basis_elems) != 0:
+        raise ValueError("seminmf: num_basis_elems must be a positive integer (one source)")
+    K = int(num_basis_elems)
+    if K != num_basis_elems or K <= 0:
+        raise ValueError("seminmf: num_basis_elems must be a positive integer")
+    m, n = V.shape
+    if K > n:
+        raise ValueError("seminmf: num_basis_elems = %d > size(V, 2) = %d: H*H' would be singular" % (K, n))
+    cfg = dict(config or {})
+    single = V.dtype == np.float32
+    rdt = np.float32 if single else np.float64
+    rng = _rng(cfg)
+    H = cfg.get("H_init", None)
+    if _isempty(H):                                                                   # seminmf.m:109-117
+        labels, _, _ = _kmeans(V, K, rng.rand(K), 100, device)
+        H = np.zeros((K, n))
+        H[labels, np.arange(n)] = 1.0
+        H = H + 0.2
+    H = np.asarray(H)
+    W = cfg.get("W_init", None)
+    if _isempty(W):                                                                   # seminmf.m:120-122
+        W = 2 * rng.rand(m, K) - 1
+    W = np.asarray(W)
+    if W.shape != (m, K):
+        raise ValueError("W_init must be %d-by-%d" % (m, K))
+    if H.shape != (K, n):
+        raise ValueError("H_init must be %d-by-%d" % (K, n))
+    wf = bool(cfg.get("W_fixed", False)) if not _isempty(cfg.get("W_fixed", None)) else False     # seminmf.m:125-132
+    hf = bool(cfg.get("H_fixed", False)) if not _isempty(cfg.get("H_fixed", None)) else False
+    maxiter = cfg.get("maxiter", None)
+    maxiter = 100 if maxiter is None or maxiter <= 0 else int(maxiter)                # seminmf.m:135-137
+    tol = cfg.get("tolerance", None)
+    tol = 1e-3 if tol is None or tol <= 0 else float(tol)                             # seminmf.m:140-142
+    Vf = _f_order(V, rdt)
+    W0 = _f_order(W, rdt)
+    H0 = _f_order(H, rdt)
+    Wout = np.zeros((m, K), order="F", dtype=rdt)
+    Hout = np.zeros((K, n), order="F", dtype=rdt)
+    cost = np.zeros(maxiter)
+    fw = np.asarray([wf], dtype=np.uint8)
+    fh = np.asarray([hf], dtype=np.uint8)
+    p = _lib.Problem()
+    p.m, p.n, p.K_total, p.T, p.dtype = m, n, K, 1, (_lib.F32 if single else _lib.F64)
+    p.V, p.W_init, p.H_init = _fptr(Vf), _fptr(W0), _fptr(H0)
+    p.divergence, p.alpha, p.beta = _lib.DIV_EUCLIDEAN, 1.0, 1.0
+    p.num_sources, p.K_s = 1, None
+    p.W_fixed, p.H_fixed = _fptr(fw), _fptr(fh)
+    p.maxiter = maxiter
+    p.tolerance = -1.0 if cfg.get("nmfx_disable_stop", False) else tol
+    p.device = int(device)
+    p.path = int(cfg.get("nmfx_path", 0))
+    r = _lib.Result()
+    r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
+    _lib.check(_lib.load().nmfx_seminmf(C.byref(p), C.byref(r)))
+    return Wout, Hout, cost[: r.cost_len].copy()
 
 
 def ReconstructFromDecomposition(W, H, device=0):
