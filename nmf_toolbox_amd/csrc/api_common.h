@@ -1,5 +1,5 @@
-// Shared by the translation units behind the C ABI (engine.hip, host_io.hip, blocking.hip, sc.hip): device guard, workspace carver,
-// hipEvent profiler, the engine object, host <-> device staging.
+// Shared by every translation unit behind the C ABI (the engine, the host staging, the blocking drivers of each algorithm, the RCCL backend): device guard,
+// workspace carver, hipEvent profiler, the engine object, host <-> device staging, and the scaffolding of a blocking call (devices and shard bounds, stop rule, call clock).
 #pragma once
 #include <cmath>
 #include <cstdarg>
@@ -225,6 +225,25 @@ void staging_quiesce();   // the pinned staging buffers hold no reference to an 
 struct IoStats { double ingest_s = 0, iterate_s = 0, egress_s = 0, h2d_bytes_host = 0, h2d_bytes_pcie = 0, d2h_bytes_host = 0;
                  double exchange_ms = 0; int exchanges_timed = 0, exchange_backend = 0; };   // multi-GPU calls: the packed exchange (nmfx_last_call_exchange)
 IoStats &io_stats();
+// the three spans of nmfx_last_call_timing: starts this thread's account afresh where the ingest begins; end(&IoStats::ingest_s), then iterate_s, then egress_s,
+// each where its span ends (the next one starts there)
+struct CallClock {
+    IoStats &io = io_stats();
+    std::chrono::steady_clock::time_point t;   // where the running span started
+    CallClock() { io = IoStats{}; t = std::chrono::steady_clock::now(); }
+    void end(double IoStats::*span) {
+        const auto now = std::chrono::steady_clock::now();
+        io.*span = std::chrono::duration<double>(now - t).count();
+        t = now;
+    }
+};
+// the stop rule of the multiplicative-update loops (nmf.m:221-224, cnmf.m:254-257, cmfwisa.m:220, seminmf.m:85-88): the cost fell, by less than the tolerance;
+// lnmf (algorithm 2, lnmf.m:84) also stops on equality.  cost[idx] is the newest entry; a negative tolerance disables the rule (NMFX extension)
+inline bool mu_stop(int algorithm, const double *cost, int idx, double tolerance) {
+    if (tolerance < 0 || idx == 0) return false;
+    if (algorithm == 2) return cost[idx] <= cost[idx - 1] && cost[idx - 1] - cost[idx] <= tolerance;
+    return cost[idx] < cost[idx - 1] && cost[idx - 1] - cost[idx] < tolerance;
+}
 nmfx_status validate_problem(const nmfx_problem *p, const nmfx_result *r, bool nmfsc, bool need_H_init = true);
 // Streams and events of the single-process multi-GPU drivers come out of a process-wide pool and go back to it, never destroyed: a MATLAB session calls
 // nmf() many times, and creating / destroying 8 streams + 32 events per call at a high call rate is what a rare host-heap corruption inside the runtime's
@@ -235,6 +254,11 @@ void unpool_stream(int device, hipStream_t st);
 void unpool_event(int device, hipEvent_t ev);
 nmfx_status pool_event_timed(int device, hipEvent_t *ev);   // the same with timing enabled (hipEventElapsedTime)
 void unpool_event_timed(int device, hipEvent_t ev);
+// the single-process multi-GPU drivers (blocking.hip, multi_sc.hip): the devices of the n_gpus shards (device_ids, or 0 .. n-1), each checked; peer mappings
+// between every pair of distinct ones; contiguous column blocks lo[g] .. lo[g + 1], as engine.shard_columns
+nmfx_status shard_devices(const nmfx_problem *p, int n, int *dev);
+nmfx_status enable_peer_access(const int *dev, int n);
+void shard_bounds(long ncols, int n, long *lo);
 nmfx_status run_nmfsc_multi(const nmfx_problem *p, nmfx_result *r);   // multi_sc.hip
 // RCCL behind the blocking multi-GPU calls, dlopen'ed (rccl_backend.hip)
 bool rccl_usable(const int *devs, int n, std::string *why);

@@ -1,7 +1,5 @@
 // Blocking host-buffer entry points of the C ABI (what the MEX gateway binds): nmf / cnmf / lnmf / constrainednmf on one GPU or
 // column-sharded over the GPUs of this process, ReconstructFromDecomposition, SortDictionary, projfunc.
-#include <chrono>
-
 #include "api_common.h"
 
 using namespace nmfx;
@@ -50,203 +48,39 @@ nmfx_status stage_init64(hipStream_t st, const nmfx_problem *p, int K, long col0
     return NMFX_OK;
 }
 
-nmfx_status run_mu(const nmfx_problem *p, nmfx_result *r, int algorithm, const int64_t *seg = nullptr, int64_t nz = 0, const void *Z_init = nullptr,
-                   void *Z_out = nullptr) {
-    TRY(validate_problem(p, r, false, algorithm != 3));
-    if (algorithm != 1 && p->T != 1) { set_error("nmf / lnmf / constrainednmf: T must be 1"); return NMFX_ERR_INVALID; }
-    if (algorithm == 3) {
-        if (!seg || !Z_init || !Z_out || nz <= 0) { set_error("constrainednmf: segments, Z_init and Z_out are required"); return NMFX_ERR_INVALID; }
-        if (p->num_sources != 1) { set_error("constrainednmf: single source only (constrainednmf.m has no multi-source form)"); return NMFX_ERR_INVALID; }
-        if (p->divergence == NMFX_DIV_EUCLIDEAN_NOCOST) { set_error("constrainednmf: unknown divergence (constrainednmf.m:204-205)"); return NMFX_ERR_INVALID; }
-    }
-    if (algorithm == 0 && p->divergence == NMFX_DIV_EUCLIDEAN_NOCOST) { set_error("nmf: unknown divergence (nmf.m:165-166)"); return NMFX_ERR_INVALID; }
-    DeviceGuard dg_;
-    TRY(check_device(p->device));
-    const int Kt = p->K_total;
-    // K rounded up to a multiple of 32 with zero, fixed components opens the fused kernels to any K <= 256 on tileable shapes: the
-    // padding contributes exact zeros to W*H and to every sum, and is never updated (it is stripped again on the way out)
-    const int dv = p->divergence;
-    // fused IS / alpha-beta (above K = 192, and the dual form alpha == 0, in two passes); constrainednmf has no dual-form kernels (fill_from_desc refuses
-    // dualz for algorithm 3): padding K there would only widen the general path
-    const bool dual_ok = (dv == NMFX_DIV_IS || dv == NMFX_DIV_AB) && Kt <= 256 && !(algorithm == 3 && dv == NMFX_DIV_AB && p->alpha == 0);
-    int Kup = (Kt + 31) / 32 * 32;
-    // cnmf: the same zero padding opens the fused shift-sum passes to any K below an instantiated (K, T) pair (K = 20, T = 8 runs as (32, 8); K = 20, T = 2 as
-    // (64, 2), the smallest pair with that context length)
-    if (algorithm == 1 && p->T > 1 && !fused_supported_T(Kup, p->T))
-        for (int kk = Kup + 32; kk <= 256; kk += 32) if (fused_supported_T(kk, p->T)) { Kup = kk; break; }
-    const bool pad_cnmf = algorithm == 1 && Kt != Kup && p->T > 1 && fused_supported_T(Kup, p->T) && p->m >= 64 && p->n >= 64 && p->path != 1 &&
-                          (dv == NMFX_DIV_KL || dv == NMFX_DIV_EUCLIDEAN || dv == NMFX_DIV_EUCLIDEAN_NOCOST ||
-                           ((dv == NMFX_DIV_IS || (dv == NMFX_DIV_AB && p->alpha != 0)) && p->m % 4 == 0));   // (IS / alpha-beta: engine.fusedT_dual, every pair since round 6)
-    const bool pad = pad_cnmf || (algorithm != 1 && Kt % 32 != 0 && (Kt <= 256 || ((dv == NMFX_DIV_KL || dv == NMFX_DIV_EUCLIDEAN) && Kt <= 2048 && p->m >= 64 && p->n >= 64)) &&   // (above 256: column blocks, engine.klw / eucw)
-                     ((p->m >= 64 && p->n >= 64) || p->path == 2) && p->path != 1 && (dv == NMFX_DIV_KL || dv == NMFX_DIV_EUCLIDEAN || dual_ok));
-    const int K = pad ? Kup : Kt;
-    std::vector<float> lw, lh;
-    std::vector<uint8_t> fw, fh;
-    expand_sources(p, K, lw, lh, fw, fh);
-    nmfx_engine_desc d{};
-    d.m = p->m; d.n_local = p->n; d.K_total = K; d.T = p->T; d.divergence = p->divergence; d.alpha = p->alpha; d.beta = p->beta;
-    d.lamW_col = lw.data(); d.lamH_row = lh.data(); d.fixW_col = fw.data(); d.fixH_row = fh.data();
-    d.device = p->device; d.stream = nullptr; d.algorithm = algorithm; d.path = p->path;
-    d.K_valid = pad ? Kt : 0;
-    size_t ws_bytes = 0, packed_count = 0;
-    TRY(nmfx_engine_workspace_bytes(&d, &ws_bytes));
-    TRY(nmfx_engine_packed_count(&d, &packed_count));
-    const size_t mn = (size_t)p->m * p->n, mKT = (size_t)p->m * K * p->T, Kn = (size_t)K * p->n;
-    DevBuf V, W, H, Z, ws, packed, Wbak, dcost, tmp;   // (tmp: K x cols staging of the un-padded row-interleaved arrays H, Z)
-    TRY(V.alloc(mn * 4)); TRY(W.alloc(mKT * 4)); TRY(H.alloc(Kn * 4)); TRY(packed.alloc(packed_count * 4));
-    // everything else this call will ever allocate comes BEFORE the workspace: a workspace that only just fits must not starve them afterwards (the retry below
-    // is for the workspace alone)
-    const size_t mKt = (size_t)p->m * Kt * p->T, Ktn = (size_t)Kt * p->n;
-    if (p->tolerance < 0) TRY(dcost.alloc(sizeof(double) * p->maxiter));
-    else if (dv == NMFX_DIV_EUCLIDEAN || dv == NMFX_DIV_EUCLIDEAN_NOCOST) TRY(Wbak.alloc(mKT * 4));   // engines of cost lag 2 (known for sure only once the engine exists)
-    if (pad) TRY(tmp.alloc(std::max(Ktn, (size_t)Kt * (size_t)(algorithm == 3 ? nz : 0)) * 4));
-    if (algorithm == 3) TRY(Z.alloc((size_t)K * nz * 4));
-    if (ws.alloc(ws_bytes) != NMFX_OK) {   // no room for the workspace with the transposed copy of V: the same problem without it (said in the descriptor, not guessed)
-        (void)hipGetLastError();
-        d.flags |= 1;
-        TRY(nmfx_engine_workspace_bytes(&d, &ws_bytes));
-        TRY(ws.alloc(ws_bytes));
-    }
-    hipStream_t st = nullptr;
-    IoStats &io = io_stats();
-    io = IoStats{};
-    const auto t0 = std::chrono::steady_clock::now();
-    TRY(upload(st, p->V, p->dtype, V.as<float>(), mn, 1.0));
-    if (pad && p->T > 1) {   // cnmf: every time slice m x K of W is padded on its own
-        const size_t sl = (size_t)p->m * Kt, slp = (size_t)p->m * K;
-        NMFX_HIP(hipMemsetAsync(W.as<float>(), 0, mKT * 4, st));
-        for (int t = 0; t < p->T; ++t) TRY(upload(st, static_cast<const char *>(p->W_init) + t * sl * dsize(p->dtype), p->dtype, W.as<float>() + t * slp, sl, 1.0));
-    } else {
-        TRY(upload(st, p->W_init, p->dtype, W.as<float>(), mKt, 1.0));   // the first K columns of the m x K_pad array
-        if (pad) NMFX_HIP(hipMemsetAsync(W.as<float>() + mKt, 0, (mKT - mKt) * 4, st));
-    }
-    if (algorithm != 3) {
-        if (pad) {
-            TRY(upload(st, p->H_init, p->dtype, tmp.as<float>(), Ktn, 1.0));
-            TRY(repack_rows(st, tmp.as<float>(), Kt, H.as<float>(), K, p->n));
-        } else TRY(upload(st, p->H_init, p->dtype, H.as<float>(), Kn, 1.0));
-    } else {   // H = Z*A is formed on the device by nmfx_engine_init (constrainednmf.m:174-177)
-        if (pad) {
-            TRY(upload(st, Z_init, p->dtype, tmp.as<float>(), (size_t)Kt * nz, 1.0));
-            TRY(repack_rows(st, tmp.as<float>(), Kt, Z.as<float>(), K, nz));
-        } else TRY(upload(st, Z_init, p->dtype, Z.as<float>(), (size_t)K * nz, 1.0));
-    }
-    // (declared after the buffers: on every return path the stream is drained and the engine destroyed BEFORE the buffers its kernels use are freed)
-    struct EngineOwner {
-        nmfx_engine *e = nullptr;
-        hipStream_t st = nullptr;
-        ~EngineOwner() { if (e) { (void)hipStreamSynchronize(st); nmfx_engine_destroy(e); } }
-    } own;
-    own.st = st;
-    nmfx_engine *e = nullptr;
-    TRY(nmfx_engine_create(&d, V.as<float>(), W.as<float>(), H.as<float>(), ws.p, ws_bytes, packed.as<float>(), &e));
-    own.e = e;
-    nmfx_status s = algorithm == 3 ? nmfx_engine_set_constraint(e, seg, nz, Z.as<float>()) : NMFX_OK;
-    NMFX_HIP(hipStreamSynchronize(st));   // (nmfx_engine_create has drained the stream already: this only closes the ingest clock)
-    const auto t1 = std::chrono::steady_clock::now();
-    if (s == NMFX_OK && p->dtype == NMFX_F64) {   // float64 host buffers: the masters start from the caller's doubles
-        DevBuf W0d, H0d;
-        s = stage_init64(st, p, K, 0, p->n, algorithm != 3, W0d, H0d);
-        if (s == NMFX_OK) s = nmfx_engine_init_f64(e, W0d.as<double>(), algorithm != 3 ? H0d.as<double>() : nullptr);
-        if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();   // W0d / H0d go out of scope
-    } else if (s == NMFX_OK) s = nmfx_engine_init(e);
-    int it = 0;
-    r->iters_run = 0;
-    auto read_cost = [&](int idx) -> nmfx_status {
-        hipError_t he = hipMemcpy(&r->cost[idx], e->cost, sizeof(double), hipMemcpyDeviceToHost);   // syncs the iteration
-        if (he != hipSuccess) { set_error("cost readback: %s", hipGetErrorString(he)); return NMFX_ERR_HIP; }
-        r->iters_run = idx + 1;
-        return NMFX_OK;
-    };
-    // nmf.m:221-224 / cnmf.m:254-257
-    auto stop = [&](int idx) {
-        if (p->tolerance < 0 || idx == 0) return false;
-        if (algorithm == 2) return r->cost[idx] <= r->cost[idx - 1] && r->cost[idx - 1] - r->cost[idx] <= p->tolerance;   // lnmf.m:84
-        return r->cost[idx] < r->cost[idx - 1] && r->cost[idx - 1] - r->cost[idx] < p->tolerance;
-    };
-    bool stopped = false;
-    const int lagk = e ? nmfx_engine_cost_lag(e) : 0;   // where cost(it-1) turns up: 1 after wstep_partial(it), 2 after wstep_finish(it), 0: cost(it) after hstep(it)
-    const bool lag = lagk != 0;
-    if (s == NMFX_OK && p->tolerance < 0) {
-        // stop rule disabled (NMFX extension): nothing is decided on the host, so nothing is read back per iteration -- the costs land in a device
-        // vector and come home once
-        s = nmfx_engine_iterate(e, p->maxiter, dcost.as<double>());
-        if (s == NMFX_OK && hipMemcpy(r->cost, dcost.p, sizeof(double) * p->maxiter, hipMemcpyDeviceToHost) != hipSuccess) { set_error("cost readback failed"); s = NMFX_ERR_HIP; }
-        if (s == NMFX_OK) r->iters_run = p->maxiter;
-        it = p->maxiter;
-        stopped = true;   // (nothing left to finish below)
-    }
-    if (s == NMFX_OK && lagk == 2 && !stopped && !Wbak.p) s = Wbak.alloc(mKT * 4);
-    for (it = stopped ? p->maxiter : 0; s == NMFX_OK && it < p->maxiter; ++it) {
-        if ((s = nmfx_engine_wstep_partial(e)) != NMFX_OK) break;
-        if (lagk == 1 && it > 0) {
-            // the fused W-step pass of iteration it also yields cost(it-1); W and H are untouched until wstep_finish, so
-            // stopping here returns exactly the state of iteration it-1 (the numerators just computed are discarded)
-            if ((s = read_cost(it - 1)) != NMFX_OK) break;
-            if (stop(it - 1)) { stopped = true; break; }
-        }
-        // Gram-form cost: cost(it-1) comes out of the W update itself, which has then already moved W -- keep the old W to hand back on a stop
-        if (lagk == 2 && it > 0 && hipMemcpyAsync(Wbak.p, W.p, mKT * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("W backup failed"); s = NMFX_ERR_HIP; break; }
-        if ((s = nmfx_engine_wstep_finish(e)) != NMFX_OK) break;
-        if (lagk == 2 && it > 0) {
-            if ((s = read_cost(it - 1)) != NMFX_OK) break;
-            if (stop(it - 1)) {
-                if (hipMemcpyAsync(W.p, Wbak.p, mKT * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("W restore failed"); s = NMFX_ERR_HIP; }
-                stopped = true;
-                break;
-            }
-        }
-        if ((s = nmfx_engine_hstep(e)) != NMFX_OK) break;
-        if (!lag) {
-            if ((s = read_cost(it)) != NMFX_OK) break;
-            if (stop(it)) { stopped = true; break; }
-        }
-    }
-    if (s == NMFX_OK && lag && !stopped) {
-        s = nmfx_engine_cost_pass(e);
-        if (s == NMFX_OK) s = read_cost(p->maxiter - 1);
-    }
-    r->cost_len = r->iters_run;
-    if (algorithm == 2) {   // lnmf.m:84-86 breaks WITHOUT trimming: the cost vector keeps its maxiter length, zero after the stop
-        for (int i = r->iters_run; i < p->maxiter; ++i) r->cost[i] = 0.0;
-        r->cost_len = p->maxiter;
-    }
-    const auto t2 = std::chrono::steady_clock::now();   // (the last cost read-back has synchronised the iterations)
-    if (pad && p->T > 1) {
-        const size_t sl = (size_t)p->m * Kt, slp = (size_t)p->m * K;
-        for (int t = 0; t < p->T && s == NMFX_OK; ++t) s = download(st, W.as<float>() + t * slp, p->dtype, static_cast<char *>(r->W) + t * sl * dsize(p->dtype), sl);
-    } else if (s == NMFX_OK) s = download(st, W.as<float>(), p->dtype, r->W, mKt);
-    if (s == NMFX_OK && pad) {
-        s = repack_rows(st, H.as<float>(), K, tmp.as<float>(), Kt, p->n);
-        if (s == NMFX_OK) s = download(st, tmp.as<float>(), p->dtype, r->H, Ktn);
-        if (s == NMFX_OK && algorithm == 3) s = repack_rows(st, Z.as<float>(), K, tmp.as<float>(), Kt, nz);
-        if (s == NMFX_OK && algorithm == 3) s = download(st, tmp.as<float>(), p->dtype, Z_out, (size_t)Kt * nz);
-    } else {
-        if (s == NMFX_OK) s = download(st, H.as<float>(), p->dtype, r->H, Kn);
-        if (s == NMFX_OK && algorithm == 3) s = download(st, Z.as<float>(), p->dtype, Z_out, (size_t)K * nz);
-    }
-    (void)hipStreamSynchronize(st);
-    nmfx_engine_destroy(e);
-    own.e = nullptr;
-    const auto t3 = std::chrono::steady_clock::now();
-    auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-    io.ingest_s = sec(t0, t1); io.iterate_s = sec(t1, t2); io.egress_s = sec(t2, t3);
-    return s;
-}
-
-// ---- nmfx_problem.n_gpus > 1: one process, one host thread, one stream + engine per device (what a MEX caller of nmf() needs) -------
-// V and H are column-sharded over the devices, W is replicated.  Per iteration ONE exchange of the packed W-step sums
+// ---- the shards of one blocking call: one stream + engine per shard, driven by one host thread (what a MEX caller of nmf() needs) -------
+// The unsharded call is ONE shard on the null stream that owns every column and exchanges nothing.  With nmfx_problem.n_gpus set, V and H are
+// column-sharded over the devices and W is replicated.  Per iteration ONE exchange of the packed W-step sums
 // (SURVEY 8(e)), done here without a collective library: every device reduces its own 1/N slice of `packed` straight out of its
 // peers' HBM over xGMI (all links in parallel, fixed summation order), then copies the other N-1 reduced slices from their owners.
 // Each slice has exactly one owner, so all replicas of W stay bit-identical.  device_ids may name one device several times
 // (N shards on one GPU): that is how the 1-GPU test box exercises this path.
+// Everything a shard's kernels touch lives in here, and the destructor body runs before the members are freed: on every return path the streams are
+// drained and the engines destroyed BEFORE the buffers they use go away.
 struct MultiDev {
+    // the call: set by the driver before the first shard is allocated
+    const nmfx_problem *p = nullptr;
+    int algorithm = 0;
+    bool sharded = false;                  // pooled streams + events, the exchange, rank0 / global ||V||^2; false: the null stream and none of them
+    int K = 0;                             // components on the device (plan_mu: K_total, or rounded up with zero padding)
+    bool pad = false;
+    int path = 0;                          // ... and the kernel path every shard is asked for
+    long nz = 0;                           // constrainednmf: columns of Z
+    std::vector<float> lw, lh;             // expand_sources
+    std::vector<uint8_t> fw, fh;
+    size_t packed_count = 0;               // floats of the packed W-step sums: the same on every shard
     int ndev = 0;
     int dev[NMFX_MAX_GPUS];
     hipStream_t st[NMFX_MAX_GPUS] = {};
     hipEvent_t evP[NMFX_MAX_GPUS] = {}, evR[NMFX_MAX_GPUS] = {}, evG[NMFX_MAX_GPUS] = {}, evH[NMFX_MAX_GPUS] = {};
     nmfx_engine *eng[NMFX_MAX_GPUS] = {};
-    DevBuf V[NMFX_MAX_GPUS], W[NMFX_MAX_GPUS], H[NMFX_MAX_GPUS], ws[NMFX_MAX_GPUS], packed[NMFX_MAX_GPUS], costh[NMFX_MAX_GPUS], tmp[NMFX_MAX_GPUS];
+    nmfx_engine_desc desc[NMFX_MAX_GPUS];
+    size_t ws_bytes[NMFX_MAX_GPUS] = {};
+    DevBuf V[NMFX_MAX_GPUS], W[NMFX_MAX_GPUS], H[NMFX_MAX_GPUS], ws[NMFX_MAX_GPUS], packed[NMFX_MAX_GPUS], costh[NMFX_MAX_GPUS];
+    DevBuf tmp[NMFX_MAX_GPUS];             // padded K: Kt x cols staging of the un-padded row-interleaved arrays H, Z
+    DevBuf Z;                              // constrainednmf (unsharded)
+    DevBuf Wbak;                           // Gram-form cost + stop rule: shard 0's W as it was before the update that produced cost(it-1)
+    DevBuf dcost;                          // unsharded call with the stop rule disabled: the device cost vector of nmfx_engine_iterate
     long lo[NMFX_MAX_GPUS + 1];
     long hL[NMFX_MAX_GPUS] = {}, hR[NMFX_MAX_GPUS] = {};   // cnmf: T-1 halo columns of H on each inner edge (and of V on the right one)
     // host side of the small device <-> host scalars (per-shard cost partials, ||V||^2): pinned.  They used to be async copies into a std::vector / the
@@ -262,10 +96,20 @@ struct MultiDev {
         if (!hpin) NMFX_HIP(hipHostMalloc(reinterpret_cast<void **>(&hpin), sizeof(double) * (NMFX_MAX_GPUS + 2), hipHostMallocPortable));
         return NMFX_OK;
     }
+    long cols(int g) const { return lo[g + 1] - lo[g]; }
+    nmfx_status drain() {
+        for (int g = 0; g < ndev; ++g) { NMFX_HIP(hipSetDevice(dev[g])); NMFX_HIP(hipStreamSynchronize(st[g])); }
+        return NMFX_OK;
+    }
+    nmfx_status alloc(int g);
+    nmfx_status alloc_workspaces();
+    nmfx_status ingest(int g, const int64_t *seg, const void *Z_init);
+    nmfx_status init(int g);
+    nmfx_status egress(int g, nmfx_result *r, void *Z_out);
     ~MultiDev() {
         for (int g = 0; g < ndev; ++g) {   // an error path may leave work in flight that reads the peers' buffers: drain every stream before anything is freed
             (void)hipSetDevice(dev[g]);
-            if (st[g]) (void)hipStreamSynchronize(st[g]);
+            (void)hipStreamSynchronize(st[g]);
         }
         staging_quiesce();   // (the ingest left its DMA-done events recorded on these streams)
         if (lease_n > 0) rccl_release(dev, lease_n);   // (every collective of this call has completed: the streams are drained)
@@ -273,13 +117,136 @@ struct MultiDev {
             (void)hipSetDevice(dev[g]);
             if (eng[g]) nmfx_engine_destroy(eng[g]);
             unpool_event(dev[g], evP[g]); unpool_event(dev[g], evR[g]); unpool_event(dev[g], evG[g]); unpool_event(dev[g], evH[g]);
-            unpool_stream(dev[g], st[g]);   // (drained above)
+            unpool_stream(dev[g], st[g]);   // (drained above; the unsharded call's null stream is nobody's to hand back)
         }
         if (ndev > 0) (void)hipSetDevice(dev[0]);
         for (hipEvent_t ev : evX) unpool_event_timed(dev[0], ev);
         if (hpin) (void)hipHostFree(hpin);
     }
 };
+
+// streams, events and every buffer of shard g except its workspace
+nmfx_status MultiDev::alloc(int g) {
+    NMFX_HIP(hipSetDevice(dev[g]));
+    ndev = g + 1;
+    if (sharded) {
+        TRY(pool_stream(dev[g], &st[g]));
+        TRY(pool_event(dev[g], &evP[g])); TRY(pool_event(dev[g], &evR[g])); TRY(pool_event(dev[g], &evG[g])); TRY(pool_event(dev[g], &evH[g]));
+    }
+    const int Kt = p->K_total, dv = p->divergence;
+    const long m = p->m, nl = cols(g), nh = hL[g] + nl + hR[g];   // H = [left halo | own columns | right halo], V = [own | right halo]
+    nmfx_engine_desc &d = desc[g];
+    d = nmfx_engine_desc{};
+    d.m = m; d.n_local = nl; d.K_total = K; d.T = p->T; d.divergence = dv; d.alpha = p->alpha; d.beta = p->beta;
+    d.halo_left = (int)hL[g]; d.halo_right = (int)hR[g]; d.n_valid = nl + hR[g];
+    d.lamW_col = lw.data(); d.lamH_row = lh.data(); d.fixW_col = fw.data(); d.fixH_row = fh.data();
+    d.device = dev[g]; d.stream = st[g]; d.algorithm = algorithm; d.path = path; d.K_valid = pad ? Kt : 0; d.col_offset = lo[g];
+    size_t pc = 0;
+    TRY(nmfx_engine_packed_count(&d, &pc));
+    if (g == 0) packed_count = pc;
+    else if (pc != packed_count) { set_error("n_gpus: shards disagree on the packed layout"); return NMFX_ERR_INVALID; }
+    const size_t mK = (size_t)m * K * p->T;
+    TRY(V[g].alloc((size_t)m * (nl + hR[g]) * 4)); TRY(W[g].alloc(mK * 4)); TRY(H[g].alloc((size_t)K * nh * 4));
+    TRY(packed[g].alloc(pc * 4)); TRY(costh[g].alloc(64));
+    if (pad) TRY(tmp[g].alloc((size_t)Kt * std::max(nl, algorithm == 3 ? nz : 0L) * 4));
+    if (algorithm == 3) TRY(Z.alloc((size_t)K * nz * 4));
+    // engines of cost lag 2 (known for sure only once the engine exists)
+    if (g == 0 && p->tolerance >= 0 && (dv == NMFX_DIV_EUCLIDEAN || dv == NMFX_DIV_EUCLIDEAN_NOCOST)) TRY(Wbak.alloc(mK * 4));
+    if (!sharded && p->tolerance < 0) TRY(dcost.alloc(sizeof(double) * p->maxiter));
+    return NMFX_OK;
+}
+
+// The workspaces come last (a workspace that only just fits must not starve anything else this call allocates) and ALL at once, with the transposed copy of
+// V; if ONE of them does not fit, every shard runs without it (flags bit 0 on all of them: said in the descriptor, not guessed).  Whether they hold that copy
+// is one decision for the whole call: the kernel path, and with it the summation order of the replicated W update, follows from the descriptor
+nmfx_status MultiDev::alloc_workspaces() {
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        bool ok = true;
+        for (int g = 0; g < ndev && ok; ++g) {
+            NMFX_HIP(hipSetDevice(dev[g]));
+            desc[g].flags = attempt == 0 ? 0 : 1;
+            TRY(nmfx_engine_workspace_bytes(&desc[g], &ws_bytes[g]));
+            if (ws[g].alloc(ws_bytes[g]) != NMFX_OK) {
+                if (attempt == 1) return NMFX_ERR_NOMEM;   // (the message of the failed allocation stands)
+                (void)hipGetLastError();
+                ok = false;
+            }
+        }
+        if (ok) break;
+        for (int g = 0; g < ndev; ++g) { NMFX_HIP(hipSetDevice(dev[g])); ws[g].release(); }
+    }
+    return NMFX_OK;
+}
+
+// host arrays -> shard g (its column block of V and H_init is a contiguous slab; W is replicated), then its engine
+nmfx_status MultiDev::ingest(int g, const int64_t *seg, const void *Z_init) {
+    NMFX_HIP(hipSetDevice(dev[g]));
+    const int Kt = p->K_total, T = p->T, dt = p->dtype;
+    const long m = p->m, nl = cols(g), nh = hL[g] + nl + hR[g];
+    const size_t sl = (size_t)m * Kt, slp = (size_t)m * K;   // one time slice of W on the host / on the device
+    float *Wd = W[g].as<float>();
+    TRY(upload(st[g], static_cast<const char *>(p->V) + (size_t)m * lo[g] * dsize(dt), dt, V[g].as<float>(), (size_t)m * (nl + hR[g]), 1.0));
+    if (pad && T > 1) {   // cnmf: every time slice m x K of W is padded on its own
+        NMFX_HIP(hipMemsetAsync(Wd, 0, slp * T * 4, st[g]));
+        for (int t = 0; t < T; ++t) TRY(upload(st[g], static_cast<const char *>(p->W_init) + t * sl * dsize(dt), dt, Wd + t * slp, sl, 1.0));
+    } else {
+        TRY(upload(st[g], p->W_init, dt, Wd, sl * T, 1.0));   // the first K_total columns of the m x K array
+        if (pad) NMFX_HIP(hipMemsetAsync(Wd + sl, 0, (slp - sl) * 4, st[g]));
+    }
+    // the row-interleaved array that comes with W: H (a padded K has no halos: plan_mu), or constrainednmf's Z -- there H = Z*A is formed on the device by
+    // nmfx_engine_init (constrainednmf.m:174-177)
+    const void *src = algorithm == 3 ? Z_init : static_cast<const char *>(p->H_init) + (size_t)Kt * (lo[g] - hL[g]) * dsize(dt);
+    float *dst = algorithm == 3 ? Z.as<float>() : H[g].as<float>();
+    const long ncols = algorithm == 3 ? nz : nh;
+    if (pad) {
+        TRY(upload(st[g], src, dt, tmp[g].as<float>(), (size_t)Kt * ncols, 1.0));
+        TRY(repack_rows(st[g], tmp[g].as<float>(), Kt, dst, K, ncols));
+    } else TRY(upload(st[g], src, dt, dst, (size_t)K * ncols, 1.0));
+    TRY(nmfx_engine_create(&desc[g], V[g].as<float>(), Wd, H[g].as<float>(), ws[g].p, ws_bytes[g], packed[g].as<float>(), &eng[g]));
+    if (algorithm == 3) TRY(nmfx_engine_set_constraint(eng[g], seg, nz, Z.as<float>()));
+    if (sharded) {
+        TRY(nmfx_engine_set_rank0(eng[g], g == 0));
+        if (hL[g] || hR[g]) TRY(nmfx_engine_defer_hstep_finish(eng[g], 1));   // V_hat / cost only once the neighbours' new columns are in
+        if (nmfx_engine_is_fused(eng[g]) != nmfx_engine_is_fused(eng[0])) { set_error("n_gpus: shards picked different kernel paths; pass path = 1"); return NMFX_ERR_UNSUPPORTED; }
+    }
+    return NMFX_OK;
+}
+
+nmfx_status MultiDev::init(int g) {
+    if (p->dtype != NMFX_F64) return nmfx_engine_init(eng[g]);
+    // float64 host buffers: the masters start from the caller's doubles (this shard's own columns of H)
+    DevBuf W0d, H0d;
+    TRY(stage_init64(st[g], p, K, lo[g], cols(g), algorithm != 3, W0d, H0d));
+    nmfx_status si = nmfx_engine_init_f64(eng[g], W0d.as<double>(), algorithm != 3 ? H0d.as<double>() : nullptr);
+    NMFX_HIP(hipStreamSynchronize(st[g]));   // W0d / H0d go out of scope
+    return si;
+}
+
+// shard g -> the caller's arrays: its own columns of H (the padding stripped again), from shard 0 also W and constrainednmf's Z
+nmfx_status MultiDev::egress(int g, nmfx_result *r, void *Z_out) {
+    NMFX_HIP(hipSetDevice(dev[g]));
+    const int Kt = p->K_total, T = p->T, dt = p->dtype;
+    const long nl = cols(g);
+    const size_t sl = (size_t)p->m * Kt, slp = (size_t)p->m * K;
+    if (g == 0) {
+        if (pad && T > 1) {
+            for (int t = 0; t < T; ++t) TRY(download(st[g], W[g].as<float>() + t * slp, dt, static_cast<char *>(r->W) + t * sl * dsize(dt), sl));
+        } else TRY(download(st[g], W[g].as<float>(), dt, r->W, sl * T));
+    }
+    char *Hh = static_cast<char *>(r->H) + (size_t)Kt * lo[g] * dsize(dt);
+    if (pad) {
+        TRY(repack_rows(st[g], H[g].as<float>(), K, tmp[g].as<float>(), Kt, nl));
+        TRY(download(st[g], tmp[g].as<float>(), dt, Hh, (size_t)Kt * nl));
+        if (algorithm == 3) {
+            TRY(repack_rows(st[g], Z.as<float>(), K, tmp[g].as<float>(), Kt, nz));
+            TRY(download(st[g], tmp[g].as<float>(), dt, Z_out, (size_t)Kt * nz));
+        }
+    } else {
+        TRY(download(st[g], H[g].as<float>() + (size_t)K * hL[g], dt, Hh, (size_t)K * nl));
+        if (algorithm == 3) TRY(download(st[g], Z.as<float>(), dt, Z_out, (size_t)K * nz));
+    }
+    return NMFX_OK;
+}
 
 nmfx_status multi_allreduce_peer(MultiDev &M, size_t count);
 // the ONE exchange of an iteration: packed[g] <- sum over the devices, in place, on every device's own stream
@@ -360,23 +327,65 @@ nmfx_status multi_halo_exchange(MultiDev &M, int K, int hh) {
     return NMFX_OK;
 }
 
-nmfx_status run_mu_multi(const nmfx_problem *p, nmfx_result *r, int algorithm) {
-    TRY(validate_problem(p, r, false, true));
-    if (algorithm != 0 && algorithm != 1 && algorithm != 2) { set_error("n_gpus > 1 is implemented for nmf, cnmf, lnmf and nmfsc"); return NMFX_ERR_UNSUPPORTED; }
-    if (algorithm != 1 && p->T != 1) { set_error("nmf / lnmf: T must be 1"); return NMFX_ERR_INVALID; }
+// Which problems get K rounded up with zero, fixed components, and which kernel path the shards are asked for.  K rounded up to a multiple of 32 opens the fused
+// kernels to any K <= 256 on tileable shapes: the padding contributes exact zeros to W*H and to every sum, and is never updated (it is stripped again on the
+// way out).  `shortest` is the column count of the shortest shard (n for the unsharded call).  Follows the eligibility rules of engine.hip::fill_from_desc
+struct MuPlan { int K; bool padded; int path; };
+MuPlan plan_mu(const nmfx_problem *p, int algorithm, bool sharded, long shortest) {
+    const int Kt = p->K_total, dv = p->divergence, T = p->T;
+    const bool tileable = p->m >= 64 && shortest >= 64;
+    MuPlan pl{Kt, false, p->path};
+    // every shard must run the same kernels (the packed layout and the summation order of the replicated W update depend on them): the fused paths want at
+    // least 64 columns, so one short shard sends all of them to the general kernels
+    if (sharded && p->path == 0 && shortest < 64) pl.path = 1;
+    int Kup = (Kt + 31) / 32 * 32;
+    bool pad;
+    if (algorithm == 1) {
+        if (sharded) return pl;   // cnmf on column shards is never padded
+        // the same zero padding opens the fused shift-sum passes to any K below an instantiated (K, T) pair (K = 20, T = 8 runs as (32, 8); K = 20, T = 2 as
+        // (64, 2), the smallest pair with that context length)
+        if (T > 1 && !fused_supported_T(Kup, T))
+            for (int kk = Kup + 32; kk <= 256; kk += 32) if (fused_supported_T(kk, T)) { Kup = kk; break; }
+        pad = Kt != Kup && T > 1 && fused_supported_T(Kup, T) && tileable && p->path != 1 &&
+              (dv == NMFX_DIV_KL || dv == NMFX_DIV_EUCLIDEAN || dv == NMFX_DIV_EUCLIDEAN_NOCOST ||
+               ((dv == NMFX_DIV_IS || (dv == NMFX_DIV_AB && p->alpha != 0)) && p->m % 4 == 0));   // (IS / alpha-beta: engine.fusedT_dual, every pair since round 6)
+    } else {
+        // fused IS / alpha-beta (above K = 192, and the dual form alpha == 0, in two passes); constrainednmf has no dual-form kernels (fill_from_desc refuses
+        // dualz for algorithm 3): padding K there would only widen the general path
+        const bool dual_ok = (dv == NMFX_DIV_IS || dv == NMFX_DIV_AB) && Kt <= 256 && !(algorithm == 3 && dv == NMFX_DIV_AB && p->alpha == 0);
+        pad = Kt % 32 != 0 && (Kt <= 256 || ((dv == NMFX_DIV_KL || dv == NMFX_DIV_EUCLIDEAN) && Kt <= 2048 && tileable)) &&   // (above 256: column blocks, engine.klw / eucw)
+              (tileable || p->path == 2) && p->path != 1 && (dv == NMFX_DIV_KL || dv == NMFX_DIV_EUCLIDEAN || dual_ok);
+    }
+    if (pad) { pl.K = Kup; pl.padded = true; }
+    return pl;
+}
+
+// nmf / cnmf / lnmf / constrainednmf (algorithm 0 .. 3) from host arrays.  sharded: nmfx_problem.n_gpus column shards (device_ids), also ONE shard with a
+// backend named; otherwise the whole problem on p->device
+nmfx_status run_mu(const nmfx_problem *p, nmfx_result *r, int algorithm, bool sharded, const int64_t *seg = nullptr, int64_t nz = 0, const void *Z_init = nullptr,
+                   void *Z_out = nullptr) {
+    TRY(validate_problem(p, r, false, algorithm != 3));
+    if (sharded && algorithm == 3) { set_error("n_gpus > 1 is implemented for nmf, cnmf, lnmf and nmfsc"); return NMFX_ERR_UNSUPPORTED; }
+    if (algorithm != 1 && p->T != 1) { set_error(sharded ? "nmf / lnmf: T must be 1" : "nmf / lnmf / constrainednmf: T must be 1"); return NMFX_ERR_INVALID; }
+    if (algorithm == 3) {
+        if (!seg || !Z_init || !Z_out || nz <= 0) { set_error("constrainednmf: segments, Z_init and Z_out are required"); return NMFX_ERR_INVALID; }
+        if (p->num_sources != 1) { set_error("constrainednmf: single source only (constrainednmf.m has no multi-source form)"); return NMFX_ERR_INVALID; }
+        if (p->divergence == NMFX_DIV_EUCLIDEAN_NOCOST) { set_error("constrainednmf: unknown divergence (constrainednmf.m:204-205)"); return NMFX_ERR_INVALID; }
+    }
     if (algorithm == 0 && p->divergence == NMFX_DIV_EUCLIDEAN_NOCOST) { set_error("nmf: unknown divergence (nmf.m:165-166)"); return NMFX_ERR_INVALID; }
-    const int N = p->n_gpus;
-    const int T = p->T, hh = T - 1;
-    if (N > NMFX_MAX_GPUS || N > p->n) { set_error("n_gpus = %d: at most %d devices and one column per device", N, NMFX_MAX_GPUS); return NMFX_ERR_INVALID; }
-    if (hh > 0 && p->n / N < hh) { set_error("cnmf on %d devices: every shard needs at least T-1 = %d columns", N, hh); return NMFX_ERR_INVALID; }
+    const int N = sharded ? p->n_gpus : 1;
+    const int hh = sharded ? p->T - 1 : 0;   // cnmf: halo columns on each inner shard edge
+    if (sharded) {
+        if (N > NMFX_MAX_GPUS || N > p->n) { set_error("n_gpus = %d: at most %d devices and one column per device", N, NMFX_MAX_GPUS); return NMFX_ERR_INVALID; }
+        if (hh > 0 && p->n / N < hh) { set_error("cnmf on %d devices: every shard needs at least T-1 = %d columns", N, hh); return NMFX_ERR_INVALID; }
+    }
     DeviceGuard dg_;
     MultiDev M;
-    TRY(M.init_host());
-    for (int g = 0; g < N; ++g) {
-        M.dev[g] = p->device_ids ? p->device_ids[g] : g;
-        TRY(check_device(M.dev[g]));
-    }
-    {   // which exchange: nmfx_problem.multi_backend, NMFX_MULTI_BACKEND for "auto"
+    M.p = p; M.algorithm = algorithm; M.sharded = sharded; M.nz = (long)nz;
+    if (sharded) {
+        TRY(M.init_host());
+        TRY(shard_devices(p, N, M.dev));
+        // which exchange: nmfx_problem.multi_backend, NMFX_MULTI_BACKEND for "auto"
         int want = p->multi_backend;
         if (want == 0) { const char *env = getenv("NMFX_MULTI_BACKEND"); if (env) want = !strcmp(env, "rccl") ? 2 : (!strcmp(env, "peer") ? 1 : 0); }
         std::string why;
@@ -385,119 +394,39 @@ nmfx_status run_mu_multi(const nmfx_problem *p, nmfx_result *r, int algorithm) {
             M.use_rccl = true;
         } else M.use_rccl = want == 0 && rccl_usable(M.dev, N, &why);
         if (M.use_rccl) { TRY(rccl_comms(M.dev, N, M.comms)); M.lease_n = N; }
+        TRY(enable_peer_access(M.dev, N));   // the reduce kernel reads the other devices' `packed` in place (and cnmf's halo copies go direct)
+    } else {
+        M.dev[0] = p->device;
+        TRY(check_device(p->device));
     }
-    for (int g = 0; g < N; ++g)      // peer mappings: the reduce kernel reads the other devices' `packed` in place (and cnmf's halo copies go direct)
-        for (int h = 0; h < N; ++h) {
-            if (M.dev[g] == M.dev[h]) continue;
-            int can = 0;
-            NMFX_HIP(hipDeviceCanAccessPeer(&can, M.dev[g], M.dev[h]));
-            if (!can) { set_error("device %d cannot access device %d as a peer", M.dev[g], M.dev[h]); return NMFX_ERR_UNSUPPORTED; }
-            NMFX_HIP(hipSetDevice(M.dev[g]));
-            hipError_t pe = hipDeviceEnablePeerAccess(M.dev[h], 0);
-            if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) { set_error("hipDeviceEnablePeerAccess(%d -> %d): %s", M.dev[g], M.dev[h], hipGetErrorString(pe)); return NMFX_ERR_HIP; }
-            (void)hipGetLastError();
-        }
-    const int Kt = p->K_total, dv = p->divergence;
-    const long m = p->m, n = p->n;
-    M.lo[0] = 0;
-    for (int g = 0; g < N; ++g) M.lo[g + 1] = M.lo[g] + n / N + (g < n % N ? 1 : 0);   // contiguous column blocks, as engine.shard_columns
-    long nmin = n;
-    for (int g = 0; g < N; ++g) nmin = std::min(nmin, M.lo[g + 1] - M.lo[g]);
-    const bool dual_ok = (dv == NMFX_DIV_IS || dv == NMFX_DIV_AB) && Kt <= 256 && !(algorithm == 3 && dv == NMFX_DIV_AB && p->alpha == 0);
-    const bool pad = algorithm != 1 && Kt % 32 != 0 && (Kt <= 256 || ((dv == NMFX_DIV_KL || dv == NMFX_DIV_EUCLIDEAN) && Kt <= 2048 && m >= 64 && nmin >= 64)) && ((m >= 64 && nmin >= 64) || p->path == 2) &&
-                     p->path != 1 && (dv == NMFX_DIV_KL || dv == NMFX_DIV_EUCLIDEAN || dual_ok);
-    const int K = pad ? (Kt + 31) / 32 * 32 : Kt;
-    std::vector<float> lw, lh;
-    std::vector<uint8_t> fw, fh;
-    expand_sources(p, K, lw, lh, fw, fh);
-    // every shard must run the same kernels (the packed layout and the summation order of the replicated W update depend on them): the fused paths want at
-    // least 64 columns, so one short shard sends all of them to the general kernels
-    const int shard_path = (p->path == 0 && nmin < 64) ? 1 : p->path;
-    const size_t mK = (size_t)m * K * T, mKt = (size_t)m * Kt * T;   // (cnmf: the T slices of W; K is never padded there)
-    size_t packed_count = 0, wsb[NMFX_MAX_GPUS] = {};
-    int kind = -1;
-    nmfx_engine_desc dd[NMFX_MAX_GPUS];
-    DevBuf Wbak;   // Gram-form cost + stop rule: device 0's W as it was before the update that produced cost(it-1)
-    // pass 1: streams, events and every buffer except the workspaces.  The workspaces come last and ALL at once, because whether they hold the transposed copy
-    // of V is one decision for the whole call (the kernel path, and with it the summation order of the replicated W update, follows from the descriptor)
+    shard_bounds(p->n, N, M.lo);
+    long shortest = p->n;
     for (int g = 0; g < N; ++g) {
-        NMFX_HIP(hipSetDevice(M.dev[g]));
-        M.ndev = g + 1;
-        TRY(pool_stream(M.dev[g], &M.st[g]));
-        TRY(pool_event(M.dev[g], &M.evP[g])); TRY(pool_event(M.dev[g], &M.evR[g])); TRY(pool_event(M.dev[g], &M.evG[g])); TRY(pool_event(M.dev[g], &M.evH[g]));
-        const long nl = M.lo[g + 1] - M.lo[g];
-        const long hL = M.hL[g] = g > 0 ? hh : 0, hR = M.hR[g] = g < N - 1 ? hh : 0;   // H = [left halo | own columns | right halo], V = [own | right halo]
-        nmfx_engine_desc &d = dd[g];
-        d = nmfx_engine_desc{};
-        d.m = m; d.n_local = nl; d.K_total = K; d.T = T; d.divergence = dv; d.alpha = p->alpha; d.beta = p->beta;
-        d.halo_left = (int)hL; d.halo_right = (int)hR; d.n_valid = nl + hR;
-        d.lamW_col = lw.data(); d.lamH_row = lh.data(); d.fixW_col = fw.data(); d.fixH_row = fh.data();
-        d.device = M.dev[g]; d.stream = M.st[g]; d.algorithm = algorithm; d.path = shard_path; d.K_valid = pad ? Kt : 0; d.col_offset = M.lo[g];
-        size_t pc = 0;
-        TRY(nmfx_engine_packed_count(&d, &pc));
-        if (g == 0) packed_count = pc;
-        else if (pc != packed_count) { set_error("n_gpus: shards disagree on the packed layout"); return NMFX_ERR_INVALID; }
-        const long nh = hL + nl + hR;
-        TRY(M.V[g].alloc((size_t)m * (nl + hR) * 4)); TRY(M.W[g].alloc(mK * 4)); TRY(M.H[g].alloc((size_t)K * nh * 4));
-        TRY(M.packed[g].alloc(pc * 4)); TRY(M.costh[g].alloc(64));
-        if (pad) TRY(M.tmp[g].alloc((size_t)Kt * nl * 4));
-        if (g == 0 && p->tolerance >= 0 && (dv == NMFX_DIV_EUCLIDEAN || dv == NMFX_DIV_EUCLIDEAN_NOCOST)) TRY(Wbak.alloc(mK * 4));
+        shortest = std::min(shortest, M.cols(g));
+        M.hL[g] = g > 0 ? hh : 0; M.hR[g] = g < N - 1 ? hh : 0;
     }
-    // pass 2: the workspaces, with the transposed copy of V; if ONE of them does not fit, every shard runs without it (flags bit 0 on all of them)
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        bool ok = true;
-        for (int g = 0; g < N && ok; ++g) {
-            NMFX_HIP(hipSetDevice(M.dev[g]));
-            dd[g].flags = attempt == 0 ? 0 : 1;
-            TRY(nmfx_engine_workspace_bytes(&dd[g], &wsb[g]));
-            if (M.ws[g].alloc(wsb[g]) != NMFX_OK) {
-                if (attempt == 1) return NMFX_ERR_NOMEM;   // (the message of the failed allocation stands)
-                (void)hipGetLastError();
-                ok = false;
-            }
-        }
-        if (ok) break;
-        for (int g = 0; g < N; ++g) { NMFX_HIP(hipSetDevice(M.dev[g])); M.ws[g].release(); }
-    }
-    // pass 3: ingest and engines.  The clocks of nmfx_last_call_timing belong to THIS call (run_mu stamps the same three spans): ingest = host arrays in +
-    // engines + init, iterate = the loop incl. the closing cost pass, egress = results out
-    IoStats &io = io_stats();
-    io = IoStats{};
-    const auto t0 = std::chrono::steady_clock::now();
+    const MuPlan plan = plan_mu(p, algorithm, sharded, shortest);
+    const int K = M.K = plan.K;
+    M.pad = plan.padded; M.path = plan.path;
+    expand_sources(p, K, M.lw, M.lh, M.fw, M.fh);
+    const size_t mK = (size_t)p->m * K * p->T;
+    for (int g = 0; g < N; ++g) TRY(M.alloc(g));
+    TRY(M.alloc_workspaces());
+    // the clocks of nmfx_last_call_timing: ingest = host arrays in + engines (sharded: + init and the first halo exchange), iterate = the loop incl. the closing
+    // cost pass, egress = results out
+    CallClock clock;
     for (int g = 0; g < N; ++g) {
-        NMFX_HIP(hipSetDevice(M.dev[g]));
-        const long nl = M.lo[g + 1] - M.lo[g], hL = M.hL[g], hR = M.hR[g], nh = hL + nl + hR;
-        const char *Vh = static_cast<const char *>(p->V) + (size_t)m * M.lo[g] * dsize(p->dtype);           // a column block is a contiguous slab
-        const char *Hh = static_cast<const char *>(p->H_init) + (size_t)Kt * (M.lo[g] - hL) * dsize(p->dtype);
-        TRY(upload(M.st[g], Vh, p->dtype, M.V[g].as<float>(), (size_t)m * (nl + hR), 1.0));
-        TRY(upload(M.st[g], p->W_init, p->dtype, M.W[g].as<float>(), mKt, 1.0));
-        if (pad) {
-            NMFX_HIP(hipMemsetAsync(M.W[g].as<float>() + mKt, 0, (mK - mKt) * 4, M.st[g]));
-            TRY(upload(M.st[g], Hh, p->dtype, M.tmp[g].as<float>(), (size_t)Kt * nl, 1.0));
-            TRY(repack_rows(M.st[g], M.tmp[g].as<float>(), Kt, M.H[g].as<float>(), K, nl));
-        } else TRY(upload(M.st[g], Hh, p->dtype, M.H[g].as<float>(), (size_t)K * nh, 1.0));
-        TRY(nmfx_engine_create(&dd[g], M.V[g].as<float>(), M.W[g].as<float>(), M.H[g].as<float>(), M.ws[g].p, wsb[g], M.packed[g].as<float>(), &M.eng[g]));
-        TRY(nmfx_engine_set_rank0(M.eng[g], g == 0));
-        if (hL || hR) TRY(nmfx_engine_defer_hstep_finish(M.eng[g], 1));   // V_hat / cost only once the neighbours' new columns are in
-        const int kd = nmfx_engine_is_fused(M.eng[g]);
-        if (kind < 0) kind = kd;
-        else if (kd != kind) { set_error("n_gpus: shards picked different kernel paths; pass path = 1"); return NMFX_ERR_UNSUPPORTED; }
-        if (p->dtype == NMFX_F64) {   // float64 host buffers: the masters start from the caller's doubles (this shard's own columns of H)
-            DevBuf W0d, H0d;
-            TRY(stage_init64(M.st[g], p, K, M.lo[g], nl, true, W0d, H0d));
-            nmfx_status si = nmfx_engine_init_f64(M.eng[g], W0d.as<double>(), H0d.as<double>());
-            NMFX_HIP(hipStreamSynchronize(M.st[g]));   // W0d / H0d go out of scope
-            TRY(si);
-        } else TRY(nmfx_engine_init(M.eng[g]));
+        TRY(M.ingest(g, seg, Z_init));
+        if (!sharded) { TRY(M.drain()); clock.end(&IoStats::ingest_s); }
+        TRY(M.init(g));
     }
     if (hh > 0) {   // the halo columns were scaled as fp32 copies (cnmf.m:165): fetch the owners' images instead, so that every shard sees the same H
         TRY(multi_halo_exchange(M, K, hh));
         for (int g = 0; g < N; ++g) TRY(nmfx_engine_hstep_finish(M.eng[g]));   // (paths that keep V_hat: refreshed with the final halos)
-        for (int g = 0; g < N; ++g) { NMFX_HIP(hipSetDevice(M.dev[g])); NMFX_HIP(hipStreamSynchronize(M.st[g])); }
+        TRY(M.drain());
     }
-    const int lagk = nmfx_engine_cost_lag(M.eng[0]);   // 1: cost(it-1) after wstep_partial(it); 2: after wstep_finish(it) (Gram-form cost); 0: cost(it) after hstep(it)
-    const bool lag = lagk != 0;
-    {   // Gram-form cost: every shard's mode decision uses the GLOBAL ||V||^2
+    const int lagk = nmfx_engine_cost_lag(M.eng[0]);   // where cost(it-1) turns up: 1 after wstep_partial(it); 2 after wstep_finish(it) (Gram-form cost); 0: cost(it) after hstep(it)
+    if (sharded) {   // Gram-form cost: every shard's mode decision uses the GLOBAL ||V||^2
         double vv = 0.0;
         double &part = M.hpin[NMFX_MAX_GPUS], &vvp = M.hpin[NMFX_MAX_GPUS + 1];
         for (int g = 0; g < N; ++g) {
@@ -512,93 +441,94 @@ nmfx_status run_mu_multi(const nmfx_problem *p, nmfx_result *r, int algorithm) {
             vvp = vv;
             NMFX_HIP(hipMemcpyAsync(M.costh[g].p, &vvp, sizeof(double), hipMemcpyHostToDevice, M.st[g]));
             TRY(nmfx_engine_sumvv_set_global(M.eng[g], M.costh[g].as<double>()));
-            NMFX_HIP(hipStreamSynchronize(M.st[g]));   // vv is a stack variable
+            NMFX_HIP(hipStreamSynchronize(M.st[g]));
         }
     }
-    if (lagk == 2 && p->tolerance >= 0 && !Wbak.p) { NMFX_HIP(hipSetDevice(M.dev[0])); TRY(Wbak.alloc(mK * 4)); }
-    for (int g = 0; g < N; ++g) { NMFX_HIP(hipSetDevice(M.dev[g])); NMFX_HIP(hipStreamSynchronize(M.st[g])); }   // closes the ingest clock (init queued its kernels)
-    const auto t1 = std::chrono::steady_clock::now();
-    double *hc = M.hpin;   // pinned: the 8-byte read-backs land by DMA, not through the runtime's staging of pageable memory (see MultiDev::hpin)
-    auto read_cost = [&](int idx) -> nmfx_status {   // cost = sum of the shards' partials (the lambda*|W| term lives on device 0 only)
-        for (int g = 0; g < N; ++g) {
-            NMFX_HIP(hipSetDevice(M.dev[g]));
-            NMFX_HIP(hipMemcpyAsync(&hc[g], M.eng[g]->cost, sizeof(double), hipMemcpyDeviceToHost, M.st[g]));
+    if (lagk == 2 && p->tolerance >= 0 && !M.Wbak.p) { NMFX_HIP(hipSetDevice(M.dev[0])); TRY(M.Wbak.alloc(mK * 4)); }
+    if (sharded) { TRY(M.drain()); clock.end(&IoStats::ingest_s); }   // (init queued its kernels)
+    auto read_cost = [&](int idx) -> nmfx_status {
+        if (!sharded) {
+            hipError_t he = hipMemcpy(&r->cost[idx], M.eng[0]->cost, sizeof(double), hipMemcpyDeviceToHost);   // syncs the iteration
+            if (he != hipSuccess) { set_error("cost readback: %s", hipGetErrorString(he)); return NMFX_ERR_HIP; }
+        } else {   // cost = sum of the shards' partials (the lambda*|W| term lives on device 0 only); the 8-byte read-backs land by DMA in pinned memory (MultiDev::hpin)
+            for (int g = 0; g < N; ++g) {
+                NMFX_HIP(hipSetDevice(M.dev[g]));
+                NMFX_HIP(hipMemcpyAsync(&M.hpin[g], M.eng[g]->cost, sizeof(double), hipMemcpyDeviceToHost, M.st[g]));
+            }
+            double c = 0.0;
+            for (int g = 0; g < N; ++g) { NMFX_HIP(hipSetDevice(M.dev[g])); NMFX_HIP(hipStreamSynchronize(M.st[g])); c += M.hpin[g]; }
+            r->cost[idx] = c;
         }
-        double c = 0.0;
-        for (int g = 0; g < N; ++g) { NMFX_HIP(hipSetDevice(M.dev[g])); NMFX_HIP(hipStreamSynchronize(M.st[g])); c += hc[g]; }
-        r->cost[idx] = c;
         r->iters_run = idx + 1;
         return NMFX_OK;
     };
-    auto stop = [&](int idx) {
-        if (p->tolerance < 0 || idx == 0) return false;
-        if (algorithm == 2) return r->cost[idx] <= r->cost[idx - 1] && r->cost[idx - 1] - r->cost[idx] <= p->tolerance;   // lnmf.m:84
-        return r->cost[idx] < r->cost[idx - 1] && r->cost[idx - 1] - r->cost[idx] < p->tolerance;                         // nmf.m:221
-    };
+    auto stop = [&](int idx) { return mu_stop(algorithm, r->cost, idx, p->tolerance); };
     r->iters_run = 0;
-    bool stopped = false;
-    for (int it = 0; it < p->maxiter; ++it) {
-        for (int g = 0; g < N; ++g) TRY(nmfx_engine_wstep_partial(M.eng[g]));
-        if (lagk == 1 && it > 0) {
-            TRY(read_cost(it - 1));
-            if (stop(it - 1)) { stopped = true; break; }
-        }
-        TRY(multi_allreduce(M, packed_count));
-        if (lagk == 2 && it > 0 && Wbak.p) { NMFX_HIP(hipSetDevice(M.dev[0])); NMFX_HIP(hipMemcpyAsync(Wbak.p, M.W[0].p, mK * 4, hipMemcpyDeviceToDevice, M.st[0])); }
-        for (int g = 0; g < N; ++g) TRY(nmfx_engine_wstep_finish(M.eng[g]));
-        if (lagk == 2 && it > 0 && p->tolerance >= 0) {
-            TRY(read_cost(it - 1));
-            if (stop(it - 1)) {   // the W that is handed back (device 0's replica) as it was when iteration it-1 ended; H has not moved yet
-                NMFX_HIP(hipSetDevice(M.dev[0]));
-                NMFX_HIP(hipMemcpyAsync(M.W[0].p, Wbak.p, mK * 4, hipMemcpyDeviceToDevice, M.st[0]));
-                stopped = true;
-                break;
+    if (!sharded && p->tolerance < 0) {
+        // stop rule disabled (NMFX extension): nothing is decided on the host, so nothing is read back per iteration -- the costs land in a device
+        // vector and come home once
+        TRY(nmfx_engine_iterate(M.eng[0], p->maxiter, M.dcost.as<double>()));
+        if (hipMemcpy(r->cost, M.dcost.p, sizeof(double) * p->maxiter, hipMemcpyDeviceToHost) != hipSuccess) { set_error("cost readback failed"); return NMFX_ERR_HIP; }
+        r->iters_run = p->maxiter;
+    } else {
+        bool stopped = false;
+        for (int it = 0; it < p->maxiter; ++it) {
+            for (int g = 0; g < N; ++g) TRY(nmfx_engine_wstep_partial(M.eng[g]));
+            if (lagk == 1 && it > 0) {
+                // the fused W-step pass of iteration it also yields cost(it-1); W and H are untouched until wstep_finish, so
+                // stopping here returns exactly the state of iteration it-1 (the numerators just computed are discarded)
+                TRY(read_cost(it - 1));
+                if (stop(it - 1)) { stopped = true; break; }
             }
-        } else if (lagk == 2 && it > 0) TRY(read_cost(it - 1));
-        for (int g = 0; g < N; ++g) TRY(nmfx_engine_hstep(M.eng[g]));
-        if (hh > 0) {
-            TRY(multi_halo_exchange(M, K, hh));
-            for (int g = 0; g < N; ++g) TRY(nmfx_engine_hstep_finish(M.eng[g]));
+            if (sharded) TRY(multi_allreduce(M, M.packed_count));
+            // Gram-form cost: cost(it-1) comes out of the W update itself, which has then already moved W -- keep the old W to hand back on a stop
+            if (lagk == 2 && it > 0 && M.Wbak.p) {
+                NMFX_HIP(hipSetDevice(M.dev[0]));
+                if (hipMemcpyAsync(M.Wbak.p, M.W[0].p, mK * 4, hipMemcpyDeviceToDevice, M.st[0]) != hipSuccess) { set_error("W backup failed"); return NMFX_ERR_HIP; }
+            }
+            for (int g = 0; g < N; ++g) TRY(nmfx_engine_wstep_finish(M.eng[g]));
+            if (lagk == 2 && it > 0) {
+                TRY(read_cost(it - 1));
+                if (stop(it - 1)) {   // the W that is handed back (shard 0's replica) as it was when iteration it-1 ended; H has not moved yet
+                    NMFX_HIP(hipSetDevice(M.dev[0]));
+                    if (hipMemcpyAsync(M.W[0].p, M.Wbak.p, mK * 4, hipMemcpyDeviceToDevice, M.st[0]) != hipSuccess) { set_error("W restore failed"); return NMFX_ERR_HIP; }
+                    stopped = true;
+                    break;
+                }
+            }
+            for (int g = 0; g < N; ++g) TRY(nmfx_engine_hstep(M.eng[g]));
+            if (hh > 0) {
+                TRY(multi_halo_exchange(M, K, hh));
+                for (int g = 0; g < N; ++g) TRY(nmfx_engine_hstep_finish(M.eng[g]));
+            }
+            if (lagk == 0) {
+                TRY(read_cost(it));
+                if (stop(it)) { stopped = true; break; }
+            }
         }
-        if (!lag) {
-            TRY(read_cost(it));
-            if (stop(it)) { stopped = true; break; }
+        if (lagk != 0 && !stopped) {
+            for (int g = 0; g < N; ++g) TRY(nmfx_engine_cost_pass(M.eng[g]));
+            TRY(read_cost(p->maxiter - 1));
         }
-    }
-    if (lag && !stopped) {
-        for (int g = 0; g < N; ++g) TRY(nmfx_engine_cost_pass(M.eng[g]));
-        TRY(read_cost(p->maxiter - 1));
     }
     r->cost_len = r->iters_run;
-    if (algorithm == 2) {
+    if (algorithm == 2) {   // lnmf.m:84-86 breaks WITHOUT trimming: the cost vector keeps its maxiter length, zero after the stop
         for (int i = r->iters_run; i < p->maxiter; ++i) r->cost[i] = 0.0;
         r->cost_len = p->maxiter;
     }
-    for (int g = 0; g < N; ++g) { NMFX_HIP(hipSetDevice(M.dev[g])); NMFX_HIP(hipStreamSynchronize(M.st[g])); }   // (a stop leaves the speculative W-step partials of the other shards in flight)
-    const auto t2 = std::chrono::steady_clock::now();
-    {   // the exchange as device 0's stream saw it
+    TRY(M.drain());   // (a stop leaves the speculative W-step partials of the other shards in flight)
+    clock.end(&IoStats::iterate_s);
+    if (sharded) {   // the exchange as device 0's stream saw it
+        IoStats &io = io_stats();
         io.exchange_backend = M.use_rccl ? 2 : 1; io.exchange_ms = 0; io.exchanges_timed = 0;
-        NMFX_HIP(hipSetDevice(M.dev[0]));
-        NMFX_HIP(hipStreamSynchronize(M.st[0]));
         for (int i = 0; i < M.nx; ++i) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, M.evX[2 * i], M.evX[2 * i + 1]) == hipSuccess) { io.exchange_ms += ms; io.exchanges_timed++; } else (void)hipGetLastError();
         }
     }
-    for (int g = 0; g < N; ++g) {
-        NMFX_HIP(hipSetDevice(M.dev[g]));
-        const long nl = M.lo[g + 1] - M.lo[g];
-        if (g == 0) TRY(download(M.st[g], M.W[g].as<float>(), p->dtype, r->W, mKt));
-        char *Hh = static_cast<char *>(r->H) + (size_t)Kt * M.lo[g] * dsize(p->dtype);
-        if (pad) {
-            TRY(repack_rows(M.st[g], M.H[g].as<float>(), K, M.tmp[g].as<float>(), Kt, nl));
-            TRY(download(M.st[g], M.tmp[g].as<float>(), p->dtype, Hh, (size_t)Kt * nl));
-        } else TRY(download(M.st[g], M.H[g].as<float>() + (size_t)K * M.hL[g], p->dtype, Hh, (size_t)K * nl));
-    }
-    for (int g = 0; g < N; ++g) { NMFX_HIP(hipSetDevice(M.dev[g])); NMFX_HIP(hipStreamSynchronize(M.st[g])); }
-    const auto t3 = std::chrono::steady_clock::now();
-    auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-    io.ingest_s = sec(t0, t1); io.iterate_s = sec(t1, t2); io.egress_s = sec(t2, t3);
+    for (int g = 0; g < N; ++g) TRY(M.egress(g, r, Z_out));
+    TRY(M.drain());
+    clock.end(&IoStats::egress_s);
     return NMFX_OK;
 }
 
@@ -608,16 +538,16 @@ extern "C" {
 
 // n_gpus / device_ids: a one-entry list names THE device (it overrides p->device); more entries shard the columns
 static nmfx_status dispatch_mu(const nmfx_problem *p, nmfx_result *r, int algorithm) {
-    if (!p) return run_mu(p, r, algorithm);
-    if (p->n_gpus > 1 || (p->n_gpus == 1 && p->multi_backend != 0)) return run_mu_multi(p, r, algorithm);   // (one shard through the sharded driver: how a 1-GPU box runs the RCCL branch)
-    if (p->n_gpus == 1 && p->device_ids) { nmfx_problem q = *p; q.device = p->device_ids[0]; return run_mu(&q, r, algorithm); }
-    return run_mu(p, r, algorithm);
+    if (!p) return run_mu(p, r, algorithm, false);
+    if (p->n_gpus > 1 || (p->n_gpus == 1 && p->multi_backend != 0)) return run_mu(p, r, algorithm, true);   // (one shard with a backend named: how a 1-GPU box runs the RCCL branch)
+    if (p->n_gpus == 1 && p->device_ids) { nmfx_problem q = *p; q.device = p->device_ids[0]; return run_mu(&q, r, algorithm, false); }
+    return run_mu(p, r, algorithm, false);
 }
 nmfx_status nmfx_nmf(const nmfx_problem *p, nmfx_result *r) { return dispatch_mu(p, r, 0); }
 nmfx_status nmfx_cnmf(const nmfx_problem *p, nmfx_result *r) { return dispatch_mu(p, r, 1); }
 nmfx_status nmfx_lnmf(const nmfx_problem *p, nmfx_result *r) { return dispatch_mu(p, r, 2); }
 nmfx_status nmfx_constrainednmf(const nmfx_problem *p, const int64_t *segments, int64_t nz, const void *Z_init, nmfx_result *r, void *Z_out) {
-    return run_mu(p, r, 3, segments, nz, Z_init, Z_out);
+    return run_mu(p, r, 3, false, segments, nz, Z_init, Z_out);
 }
 
 nmfx_status nmfx_reconstruct(int64_t m, int64_t n, int32_t K, int32_t T, int32_t dtype, const void *W, const void *H, void *V_hat,

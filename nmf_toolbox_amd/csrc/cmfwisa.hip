@@ -366,9 +366,7 @@ nmfx_status run_cmfwisa(const nmfx_problem *p, const void *V_imag, const void *P
     uint8_t *pf_d = cv.take<uint8_t>(I);
     hipStream_t st = nullptr;
     StreamDrain drain_(st);   // (after the host vectors and the buffers: drained before they go away on any return path)
-    IoStats &io = io_stats();
-    io = IoStats{};
-    const auto t0 = std::chrono::steady_clock::now();
+    CallClock clock;
     NMFX_HIP(hipMemcpyAsync(lam_d, lam.data(), K * 8, hipMemcpyHostToDevice, st));
     NMFX_HIP(hipMemcpyAsync(rk0_d, row_k0.data(), K * 4, hipMemcpyHostToDevice, st));
     NMFX_HIP(hipMemcpyAsync(rKs_d, row_Ks.data(), K * 4, hipMemcpyHostToDevice, st));
@@ -404,7 +402,7 @@ nmfx_status run_cmfwisa(const nmfx_problem *p, const void *V_imag, const void *P
     hipLaunchKernelGGL(cmf_wcols, dim3(K), dim3(256), 0, st, W64[0].as<double>(), W64[0].as<double>(), W32[0].as<float>(), nullptr, nullptr, m, fw_d, 1);
     NMFX_HIP(hipGetLastError());
     NMFX_HIP(hipStreamSynchronize(st));   // (the caller's pageable buffers have been read)
-    const auto t1 = std::chrono::steady_clock::now();
+    clock.end(&IoStats::ingest_s);
 
     EParams ep;
     memset(&ep, 0, sizeof(ep));
@@ -457,8 +455,7 @@ nmfx_status run_cmfwisa(const nmfx_problem *p, const void *V_imag, const void *P
         ep.cur ^= 1;
         return NMFX_OK;
     };
-    // cmfwisa.m:220
-    auto stop = [&](int idx) { return p->tolerance >= 0 && idx > 0 && r->cost[idx] < r->cost[idx - 1] && r->cost[idx - 1] - r->cost[idx] < p->tolerance; };
+    auto stop = [&](int idx) { return mu_stop(0, r->cost, idx, p->tolerance); };   // cmfwisa.m:220
     bool stopped = false;
     int it = 0;
     for (; it < p->maxiter; ++it) {
@@ -479,7 +476,7 @@ nmfx_status run_cmfwisa(const nmfx_problem *p, const void *V_imag, const void *P
     }
     NMFX_HIP(hipMemcpy(r->cost, dcost.p, (size_t)it * 8, hipMemcpyDeviceToHost));
     r->cost_len = r->iters_run = it;
-    const auto t2 = std::chrono::steady_clock::now();
+    clock.end(&IoStats::iterate_s);
     if (p->dtype == NMFX_F64) {
         NMFX_HIP(hipMemcpy(r->W, W64[wc].p, mK * 8, hipMemcpyDeviceToHost));
         NMFX_HIP(hipMemcpy(r->H, H64.p, Kn * 8, hipMemcpyDeviceToHost));
@@ -503,9 +500,7 @@ nmfx_status run_cmfwisa(const nmfx_problem *p, const void *V_imag, const void *P
         }
     }
     NMFX_HIP(hipStreamSynchronize(st));
-    const auto t3 = std::chrono::steady_clock::now();
-    auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-    io.ingest_s = sec(t0, t1); io.iterate_s = sec(t1, t2); io.egress_s = sec(t2, t3);
+    clock.end(&IoStats::egress_s);
     return NMFX_OK;
 }
 

@@ -169,6 +169,32 @@ void unpool_event(int device, hipEvent_t ev) {
 
 IoStats &io_stats() { return g_io; }
 
+nmfx_status shard_devices(const nmfx_problem *p, int n, int *dev) {
+    for (int g = 0; g < n; ++g) {
+        dev[g] = p->device_ids ? p->device_ids[g] : g;
+        TRY(check_device(dev[g]));
+    }
+    return NMFX_OK;
+}
+nmfx_status enable_peer_access(const int *dev, int n) {
+    for (int g = 0; g < n; ++g)
+        for (int h = 0; h < n; ++h) {
+            if (dev[g] == dev[h]) continue;
+            int can = 0;
+            NMFX_HIP(hipDeviceCanAccessPeer(&can, dev[g], dev[h]));
+            if (!can) { set_error("device %d cannot access device %d as a peer", dev[g], dev[h]); return NMFX_ERR_UNSUPPORTED; }
+            NMFX_HIP(hipSetDevice(dev[g]));
+            hipError_t pe = hipDeviceEnablePeerAccess(dev[h], 0);
+            if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) { set_error("hipDeviceEnablePeerAccess(%d -> %d): %s", dev[g], dev[h], hipGetErrorString(pe)); return NMFX_ERR_HIP; }
+            (void)hipGetLastError();
+        }
+    return NMFX_OK;
+}
+void shard_bounds(long ncols, int n, long *lo) {
+    lo[0] = 0;
+    for (int g = 0; g < n; ++g) lo[g + 1] = lo[g] + ncols / n + (g < ncols % n ? 1 : 0);
+}
+
 // The staging buffers remember the event of their last DMA (PinnedPool::pend_dev) and wait for it before they are refilled -- by then possibly in a LATER call.
 // A multi-device call records those events on ITS OWN streams, which go back to the pool (or, with NMFX_NO_POOL, are destroyed) when it ends: settle the
 // bookkeeping while the streams still exist, so that no later call ever synchronises an event whose stream is gone.  The callers have drained their streams.

@@ -157,24 +157,10 @@ nmfx_status run_nmfsc_multi(const nmfx_problem *p, nmfx_result *r) {
     DeviceGuard dg_;
     ScMulti M;
     ThreadComm &C = M.C;
-    for (int g = 0; g < N; ++g) {
-        C.dev[g] = p->device_ids ? p->device_ids[g] : g;
-        TRY(check_device(C.dev[g]));
-    }
-    for (int g = 0; g < N; ++g)
-        for (int h = 0; h < N; ++h) {
-            if (C.dev[g] == C.dev[h]) continue;
-            int can = 0;
-            NMFX_HIP(hipDeviceCanAccessPeer(&can, C.dev[g], C.dev[h]));
-            if (!can) { set_error("device %d cannot access device %d as a peer", C.dev[g], C.dev[h]); return NMFX_ERR_UNSUPPORTED; }
-            NMFX_HIP(hipSetDevice(C.dev[g]));
-            hipError_t pe = hipDeviceEnablePeerAccess(C.dev[h], 0);
-            if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) { set_error("hipDeviceEnablePeerAccess(%d -> %d): %s", C.dev[g], C.dev[h], hipGetErrorString(pe)); return NMFX_ERR_HIP; }
-            (void)hipGetLastError();
-        }
+    TRY(shard_devices(p, N, C.dev));
+    TRY(enable_peer_access(C.dev, N));
     long lo[NMFX_MAX_GPUS + 1];
-    lo[0] = 0;
-    for (int g = 0; g < N; ++g) lo[g + 1] = lo[g] + n / N + (g < n % N ? 1 : 0);   // contiguous column blocks, as engine.shard_columns
+    shard_bounds(n, N, lo);
     const size_t mK = (size_t)m * K, es = dsize(p->dtype);
     for (int g = 0; g < N; ++g) {
         NMFX_HIP(hipSetDevice(C.dev[g]));

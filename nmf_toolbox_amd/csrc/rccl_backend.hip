@@ -103,7 +103,7 @@ bool rccl_usable(const int *devs, int n, std::string *why) {
 }
 
 // check the communicators of this device list out for one blocking call (created on first use, cached); comms[g] belongs to devs[g].  Blocks while another
-// thread holds the same set; rccl_release hands it back (RcclLease in blocking.hip does that on every return path)
+// thread holds the same set; rccl_release hands it back (the destructor of MultiDev in blocking.hip does that on every return path)
 nmfx_status rccl_comms(const int *devs, int n, void **comms_out) {
     std::unique_lock<std::mutex> lk(g_mu);
     if (!load_api()) { set_error("RCCL backend: librccl could not be loaded (%s)", g_api.error.c_str()); return NMFX_ERR_UNSUPPORTED; }

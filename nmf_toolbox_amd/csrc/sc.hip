@@ -635,9 +635,7 @@ nmfx_status run_cnmfsc(const nmfx_problem *p, nmfx_result *r) {
     g_sc_prof.st = st;
     if (g_sc_prof.on) { g_sc_prof.events.clear(); g_sc_prof.pool_used = 0; }
     Profiler *pf = &g_sc_prof;
-    IoStats &io = io_stats();
-    io = IoStats{};
-    const auto t_in = std::chrono::steady_clock::now();
+    CallClock clock;
     double sW = p->sc_W_sparsity, sH = p->sc_H_sparsity, L1a = 0, L1s = 0;
     if (sW > 0) { if (sW > 1) sW = 1; L1a = std::sqrt((double)m) - (std::sqrt((double)m) - 1) * sW; }   // cnmfsc.m:100-104
     if (sH > 0) { if (sH > 1) sH = 1; L1s = std::sqrt((double)n) - (std::sqrt((double)n) - 1) * sH; }   // cnmfsc.m:116-120
@@ -795,7 +793,7 @@ nmfx_status run_cnmfsc(const nmfx_problem *p, nmfx_result *r) {
     double stepH = 1.0;
     std::vector<double> stepW(T, 1.0);                                                           // cnmfsc.m:147-148
     TRY(rfd(W, H, &r->cost[0]));                                                                 // cnmfsc.m:152-153  (reads the objective: the uploads have drained)
-    const auto t_it = std::chrono::steady_clock::now();
+    clock.end(&IoStats::ingest_s);
     g_iter_t.clear();
     int ncost = p->maxiter + 1, nH = 0, nW = 0;
     bool early = false;
@@ -945,7 +943,7 @@ nmfx_status run_cnmfsc(const nmfx_problem *p, nmfx_result *r) {
         }
         NMFX_HIP(hipMemcpyAsync(W0, W, mKT * 4, hipMemcpyDeviceToDevice, st));                   // W0 = W   cnmfsc.m:266
         TRY(rfd(W0, H, &r->cost[it]));                                                           // cnmfsc.m:269-270
-        g_iter_t.push_back(std::chrono::duration<double>(std::chrono::steady_clock::now() - t_it).count());   // (the objective was read on the host: the iteration is complete)
+        g_iter_t.push_back(std::chrono::duration<double>(std::chrono::steady_clock::now() - clock.t).count());   // (the objective was read on the host: the iteration is complete)
         if (p->tolerance >= 0 && it > 1 && r->cost[it] < r->cost[it - 1] && r->cost[it - 1] - r->cost[it] < p->tolerance) {   // cnmfsc.m:273-276
             ncost = it + 1;
             break;
@@ -957,11 +955,10 @@ nmfx_status run_cnmfsc(const nmfx_problem *p, nmfx_result *r) {
     r->converged_early = early ? 1 : 0;
     if (r->tries_H) for (int i = nH; i < p->maxiter; ++i) r->tries_H[i] = 0;
     if (r->tries_W) for (int i = nW; i < p->maxiter * T; ++i) r->tries_W[i] = 0;
-    const auto t_out = std::chrono::steady_clock::now();
+    clock.end(&IoStats::iterate_s);
     TRY(download(st, W, p->dtype, r->W, mKT));
     TRY(download(st, H, p->dtype, r->H, Kn));
-    auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-    io.ingest_s = sec(t_in, t_it); io.iterate_s = sec(t_it, t_out); io.egress_s = sec(t_out, std::chrono::steady_clock::now());
+    clock.end(&IoStats::egress_s);
     return NMFX_OK;
 }
 

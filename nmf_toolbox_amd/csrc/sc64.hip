@@ -127,10 +127,8 @@ nmfx_status run_nmfsc_f64(const nmfx_problem *p, nmfx_result *r) {
     } ps{p->device};
     TRY(pool_stream(p->device, &ps.st));
     hipStream_t st = ps.st;
-    IoStats &io = io_stats();
-    io = IoStats{};
     sc_hooks_reset();
-    const auto t_in = std::chrono::steady_clock::now();
+    CallClock clock;
     double sW = p->sc_W_sparsity, sH = p->sc_H_sparsity, L1a = 0, L1s = 0;
     if (sW > 0) { if (sW > 1) sW = 1; L1a = std::sqrt((double)m) - (std::sqrt((double)m) - 1) * sW; }   // nmfsc.m:89-93
     if (sH > 0) { if (sH > 1) sH = 1; L1s = std::sqrt((double)n) - (std::sqrt((double)n) - 1) * sH; }   // nmfsc.m:102-106
@@ -174,8 +172,7 @@ nmfx_status run_nmfsc_f64(const nmfx_problem *p, nmfx_result *r) {
     };
     double stepH = p->sc_stepsize_H0 > 0 ? p->sc_stepsize_H0 : 1.0, stepW = p->sc_stepsize_W0 > 0 ? p->sc_stepsize_W0 : 1.0;   // nmfsc.m:133-134
     TRY(recon_obj(Wd, HTd, &r->cost[0]));   // nmfsc.m:138-139
-    const auto t_it = std::chrono::steady_clock::now();
-    io.ingest_s = std::chrono::duration<double>(t_it - t_in).count();
+    clock.end(&IoStats::ingest_s);
     int ncost = p->maxiter + 1, nH = 0, nW = 0;
     bool early = false;
     for (int it = 1; it <= p->maxiter && !early; ++it) {
@@ -232,7 +229,7 @@ nmfx_status run_nmfsc_f64(const nmfx_problem *p, nmfx_result *r) {
             NMFX_HIP(hipGetLastError());
         }
         TRY(recon_obj(Wd, HTd, &r->cost[it]));                                                      // nmfsc.m:237-238
-        sc_hooks_iteration_done(t_it);
+        sc_hooks_iteration_done(clock.t);
         if (p->tolerance >= 0 && it > 1 && r->cost[it] < r->cost[it - 1] && r->cost[it - 1] - r->cost[it] < p->tolerance) {   // nmfsc.m:241-244
             ncost = it + 1;
             break;
@@ -244,8 +241,7 @@ nmfx_status run_nmfsc_f64(const nmfx_problem *p, nmfx_result *r) {
     r->converged_early = early ? 1 : 0;
     if (r->tries_H) for (int i = nH; i < p->maxiter; ++i) r->tries_H[i] = 0;
     if (r->tries_W) for (int i = nW; i < p->maxiter; ++i) r->tries_W[i] = 0;
-    const auto t_out = std::chrono::steady_clock::now();   // (the last objective was read on the host: the iterations are complete)
-    io.iterate_s = std::chrono::duration<double>(t_out - t_it).count();
+    clock.end(&IoStats::iterate_s);   // (the last objective was read on the host: the iterations are complete)
     hipLaunchKernelGGL(sc64_transpose_kernel, g1((long)Kn), dim3(256), 0, st, HTd, n, (long)K, Hk.as<double>());
     NMFX_HIP(hipGetLastError());
     auto egress = [&](const double *src, size_t count, void *host) -> nmfx_status {
@@ -260,7 +256,7 @@ nmfx_status run_nmfsc_f64(const nmfx_problem *p, nmfx_result *r) {
     TRY(egress(Wd, mK, r->W));
     TRY(egress(Hk.as<double>(), Kn, r->H));
     NMFX_HIP(hipStreamSynchronize(st));
-    io.egress_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_out).count();
+    clock.end(&IoStats::egress_s);
     return NMFX_OK;
 }
 

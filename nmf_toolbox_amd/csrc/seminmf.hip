@@ -694,9 +694,7 @@ nmfx_status run_seminmf(const nmfx_problem *p, nmfx_result *r) {
     int *fail = flags.as<int>(), *exact = flags.as<int>() + 1;
     hipStream_t st = nullptr;
     StreamDrain drain_(st);
-    IoStats &io = io_stats();
-    io = IoStats{};
-    const auto t0 = std::chrono::steady_clock::now();
+    CallClock clock;
     NMFX_HIP(hipMemsetAsync(flags.p, 0, 256, st));
     NMFX_HIP(hipMemsetAsync(Wt32.p, 0, (size_t)KP * m * 4, st));   // (rows K .. KP-1 stay zero: the padded components contribute nothing to B)
     float *V = Vd.as<float>();
@@ -717,7 +715,7 @@ nmfx_status run_seminmf(const nmfx_problem *p, nmfx_result *r) {
     hipLaunchKernelGGL(sn_sum, dim3(1), dim3(256), 0, st, parts.as<double>(), nb_v, vv.as<double>());
     NMFX_HIP(hipGetLastError());
     NMFX_HIP(hipStreamSynchronize(st));   // (the caller's pageable buffers have been read)
-    const auto t1 = std::chrono::steady_clock::now();
+    clock.end(&IoStats::ingest_s);
 
     auto n_product = [&]() -> nmfx_status {   // N = V*H' in float64 (A: V fp32, B: Ht float64)
         return gemm64(st, m, K, n, nullptr, V, m, Ht.as<double>(), nullptr, n, N.as<double>(), nullptr, m);
@@ -780,8 +778,7 @@ nmfx_status run_seminmf(const nmfx_problem *p, nmfx_result *r) {
         NMFX_HIP(hipGetLastError());
         return NMFX_OK;
     };
-    // seminmf.m:85-88
-    auto stop = [&](int idx) { return p->tolerance >= 0 && idx > 0 && r->cost[idx] < r->cost[idx - 1] && r->cost[idx - 1] - r->cost[idx] < p->tolerance; };
+    auto stop = [&](int idx) { return mu_stop(0, r->cost, idx, p->tolerance); };   // seminmf.m:85-88
     int it = 0;
     for (; it < p->maxiter; ++it) {
         if (!wf) { TRY(w_step(it)); TRY(wt_image()); }
@@ -805,7 +802,7 @@ nmfx_status run_seminmf(const nmfx_problem *p, nmfx_result *r) {
     }
     NMFX_HIP(hipMemcpy(r->cost, dcost.p, (size_t)it * 8, hipMemcpyDeviceToHost));
     r->cost_len = r->iters_run = it;
-    const auto t2 = std::chrono::steady_clock::now();
+    clock.end(&IoStats::iterate_s);
     if (p->dtype == NMFX_F64) {
         NMFX_HIP(hipMemcpy(r->W, W64.p, mK * 8, hipMemcpyDeviceToHost));
         NMFX_HIP(hipMemcpy(r->H, H64[hc].p, Kn * 8, hipMemcpyDeviceToHost));
@@ -816,9 +813,7 @@ nmfx_status run_seminmf(const nmfx_problem *p, nmfx_result *r) {
         TRY(download(st, H32.as<float>(), p->dtype, r->H, Kn));
     }
     NMFX_HIP(hipStreamSynchronize(st));
-    const auto t3 = std::chrono::steady_clock::now();
-    auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-    io.ingest_s = sec(t0, t1); io.iterate_s = sec(t1, t2); io.egress_s = sec(t2, t3);
+    clock.end(&IoStats::egress_s);
     return NMFX_OK;
 }
 

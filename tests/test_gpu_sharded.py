@@ -1028,7 +1028,7 @@ def test_blocking_api_rccl_backend_refuses_duplicate_devices(gpu_lib):
 
 
 def test_blocking_multi_gpu_call_reports_its_own_timing(gpu_lib):
-    """run_mu_multi left nmfx_last_call_timing at whatever an EARLIER call on the thread had written (a warm-up's 4 ms for ten C3 iterations).
+    """the sharded blocking call left nmfx_last_call_timing at whatever an EARLIER call on the thread had written (a warm-up's 4 ms for ten C3 iterations).
     The three spans now belong to the call: a long sharded call after a short unsharded one reports more iterate time than the short call took in total, at
     least the time its fused passes need (2 x 2*m*n*K flop per iteration at the fp32 MFMA peak is a floor no run can beat), and they add up to no more than the
     wall time of the call"""
