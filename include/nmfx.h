@@ -15,7 +15,7 @@
  *   - there is NO CPU fallback: without a usable gfx950 device compute calls fail with
  *     NMFX_ERR_NO_DEVICE
  *   - device arithmetic is fp32 (MFMA v_mfma_f32_32x32x2_f32) with fp64 scalar/vector reductions;
- *     eps is MATLAB's 2^-52, not FLT_EPSILON
+ *     eps is MATLAB's 2^-52, not FLT_EPSILON.  nmfx_nmf_f64 is the exception: float64 throughout
  */
 #ifndef NMFX_H
 #define NMFX_H
@@ -188,6 +188,16 @@ nmfx_status nmfx_cmfwisa(const nmfx_problem *p, const void *V_imag,
  * H*H' whose Cholesky factor meets a pivot <= 0 or not finite (the message names the iteration; MATLAB warns and goes on with Inf / NaN).
  * W is never column-normalised.  result.cost needs maxiter entries and is trimmed by the stop rule like nmf's.  nmfx_last_call_timing describes it. */
 nmfx_status nmfx_seminmf(const nmfx_problem *p, nmfx_result *r);
+/* [W,H,cost] = nmf(V, num_basis_elems, config) with every quantity a double on the device -- nmf.m:1 (hot loop nmf.m:143-225) as nmfx_nmf runs it, but V, W,
+ * H and the element maps of the divergence are float64 and every m*n*K contraction runs on the fp64 matrix core (v_mfma_f64_16x16x4_f64).  A new entry
+ * point; no structure grows, so NMFX_VERSION stays 600.  Parity with the float64 reference is 1e-10 on W and H and 1e-11 on the cost at any depth, at
+ * a fraction of nmfx_nmf's rate.  dtype is the type of the HOST arrays only: NMFX_F32 arrays are widened on ingest and the results are
+ * rounded to fp32 on the way out.  Every field means what it means for nmfx_nmf (divergences euclidean, kl, is, ab including alpha == 0; several
+ * sources; sparsities; fixed factors; maxiter; tolerance, < 0 disables the stop rule; device), except: path is ignored (there is one path), and T != 1,
+ * n_gpus > 1 or multi_backend != 0 are NMFX_ERR_UNSUPPORTED.  result.cost needs maxiter entries and is trimmed by the stop rule like nmf's (the host
+ * reads 8 bytes per iteration when tolerance >= 0).  A failed device allocation is NMFX_ERR_NOMEM with the byte count in the message: the call holds
+ * 8*m*n*(1 euclidean | 2 kl | 3 is, ab) bytes plus O((m + n)*K).  nmfx_last_call_timing describes it. */
+nmfx_status nmfx_nmf_f64(const nmfx_problem *p, nmfx_result *r);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,

@@ -121,6 +121,20 @@ def _validate(V, Ks, T, config, cnmf_mode):
     return cfg, W, H, is_W_cell, is_H_cell
 
 
+_PRECISIONS = {None: False, "float32": False, "single": False, "float64": True, "double": True}
+
+
+def _precision(config, fn="nmf"):
+    """config.nmfx_precision (extension) -> True for the float64 mode: absent / None / 'float32' / 'single' is the fp32 device arithmetic of every call,
+    'float64' / 'double' runs nmf end to end in double (nmfx_nmf_f64).  Only nmf has the mode; the other functions refuse it instead of running in fp32."""
+    v = config.get("nmfx_precision", None) if config else None
+    if not (v is None or isinstance(v, str)) or v not in _PRECISIONS:
+        raise ValueError("nmfx_precision must be 'float32' ('single') or 'float64' ('double'); got %r" % (v,))
+    if _PRECISIONS[v] and fn != "nmf":
+        raise ValueError("nmfx_precision=%r: only nmf has a float64 mode; %s runs its device arithmetic in fp32" % (v, fn))
+    return _PRECISIONS[v]
+
+
 def _fptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -213,8 +227,15 @@ def _run_mu(fn, V, Ks, T, cfg, W, H, divergence, device):
 
 
 def nmf(V, num_basis_elems, config=None, device=0):
-    """[W, H, cost] = nmf(V, num_basis_elems, config)  -- nmf.m:1."""
-    V = _as_data(V)
+    """[W, H, cost] = nmf(V, num_basis_elems, config)  -- nmf.m:1.
+
+    Extension: config['nmfx_precision'] = 'float64' ('double') runs the whole factorisation in double on the device (every contraction on the fp64
+    matrix core): V, W_init and H_init travel as float64 whatever V's dtype, W and H come back as float64, parity with the reference is 1e-10 instead
+    of 1e-5.  One GPU, one path (nmfx_path is ignored; nmfx_gpus / nmfx_multi_backend are refused).  The default is unchanged."""
+    f64 = _precision(config)
+    if f64 and (config.get("nmfx_gpus", None) is not None or config.get("nmfx_multi_backend", None) is not None):
+        raise ValueError("nmfx_precision='float64' runs on one GPU: nmfx_gpus and nmfx_multi_backend cannot be combined with it")
+    V = np.asarray(V, dtype=np.float64) if f64 else _as_data(V)
     if V.ndim != 2:
         raise ValueError("V must be a matrix")
     Ks = [int(k) for k in (num_basis_elems if _is_cell(num_basis_elems) else [num_basis_elems])]   # nmf.m:114-117
@@ -224,13 +245,15 @@ def nmf(V, num_basis_elems, config=None, device=0):
         raise ValueError("alpha = 0 and beta = 0 is not supported at this time.")
     if div not in _DIV_NMF:                                                                        # nmf.m:165-166
         raise ValueError("No update equations defined for cost function with divergence type " + str(div))
-    Wl, Hl, cost = _run_mu(_lib.load().nmfx_nmf, V, Ks, 1, cfg, W, H, _DIV_NMF[div], device)
+    lib = _lib.load()
+    Wl, Hl, cost = _run_mu(lib.nmfx_nmf_f64 if f64 else lib.nmfx_nmf, V, Ks, 1, cfg, W, H, _DIV_NMF[div], device)
     Wl = [w[:, :, 0] for w in Wl]
     return (Wl if is_W_cell else Wl[0]), (Hl if is_H_cell else Hl[0]), cost                        # nmf.m:228-234
 
 
 def cnmf(V, num_basis_elems, context_len, config=None, device=0):
     """[W, H, cost] = cnmf(V, num_basis_elems, context_len, config)  -- cnmf.m:1."""
+    _precision(config, "cnmf")
     V = _as_data(V)
     if V.ndim != 2:
         raise ValueError("V must be a matrix")
@@ -252,6 +275,7 @@ def cnmf(V, num_basis_elems, context_len, config=None, device=0):
 def lnmf(V, num_basis_elems, config=None, device=0):
     """[W, H, cost] = lnmf(V, num_basis_elems, config)  -- lnmf.m:1.  `cost` has maxiter entries, zero
     after an early stop (the reference breaks without trimming, lnmf.m:84-86)."""
+    _precision(config, "lnmf")
     V = np.asarray(V, dtype=np.float64)
     if V.ndim != 2:
         raise ValueError("V must be a matrix")
@@ -308,6 +332,7 @@ def constrainednmf(V, labels, num_basis_elems, config=None, device=0):
 
     The reference draws Z with rand() inside the function (constrainednmf.m:174); `config['Z_init']` (extension) supplies it
     for reproducible runs.  A is returned dense like the reference's; config['nmfx_sparse_A'] = True returns scipy CSR instead."""
+    _precision(config, "constrainednmf")
     V = np.asarray(V, dtype=np.float64)
     if V.ndim != 2:
         raise ValueError("V must be a matrix")
@@ -404,6 +429,7 @@ def nmfsc(V, num_basis_elems, config=None, device=0, info=None):
 
     `info` (dict, optional) receives the line-search try counts and final step sizes (test aid).
     """
+    _precision(config, "nmfsc")
     V = np.asarray(V, dtype=np.float64)
     if V.ndim != 2:
         raise ValueError("V must be a matrix")
@@ -462,6 +488,7 @@ def nmfsc(V, num_basis_elems, config=None, device=0, info=None):
 
 def cnmfsc(V, num_basis_elems, context_len, config=None, device=0, info=None):
     """[W, H, cost] = cnmfsc(V, num_basis_elems, context_len, config)  -- cnmfsc.m:1."""
+    _precision(config, "cnmfsc")
     V = np.asarray(V, dtype=np.float64)
     if V.ndim != 2:
         raise ValueError("V must be a matrix")
