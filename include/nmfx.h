@@ -15,7 +15,7 @@
  *   - there is NO CPU fallback: without a usable gfx950 device compute calls fail with
  *     NMFX_ERR_NO_DEVICE
  *   - device arithmetic is fp32 (MFMA v_mfma_f32_32x32x2_f32) with fp64 scalar/vector reductions;
- *     eps is MATLAB's 2^-52, not FLT_EPSILON.  nmfx_nmf_f64 is the exception: float64 throughout
+ *     eps is MATLAB's 2^-52, not FLT_EPSILON.  nmfx_nmf_f64 and nmfx_nmf_batch are the exceptions: float64 contractions
  */
 #ifndef NMFX_H
 #define NMFX_H
@@ -198,6 +198,25 @@ nmfx_status nmfx_seminmf(const nmfx_problem *p, nmfx_result *r);
  * reads 8 bytes per iteration when tolerance >= 0).  A failed device allocation is NMFX_ERR_NOMEM with the byte count in the message: the call holds
  * 8*m*n*(1 euclidean | 2 kl | 3 is, ab) bytes plus O((m + n)*K).  nmfx_last_call_timing describes it. */
 nmfx_status nmfx_nmf_f64(const nmfx_problem *p, nmfx_result *r);
+/* `batch` independent nmf problems (nmf.m:1, hot loop nmf.m:143-225) in one call: they share m, K_total and the configuration, problem b has its own
+ * n_b = col_offsets[b + 1] - col_offsets[b] >= 1 columns, its own W_b, H_b, cost vector and stopping point.  Result b is what nmfx_nmf returns for problem b
+ * alone; a problem whose stop rule fires at iteration t keeps W(t), H(t) and a cost vector of length t while the others run on.  A new entry point; no
+ * structure grows, so NMFX_VERSION stays 600.
+ *   col_offsets  [batch + 1], col_offsets[0] = 0, strictly increasing, col_offsets[batch] = p->n = N
+ *   p->V         m x N, the problems side by side;  p->H_init  K_total x N;  p->W_init  m x K_total x batch
+ *   r->W         m x K_total x batch;  r->H  K_total x N
+ *   r->cost      maxiter x batch, column-major: problem b's costs at the top of column b, zero below cost_len[b]
+ *   cost_len     out [batch];  r->cost_len and r->iters_run hold the maximum over the batch
+ * T and num_sources must be 1; W_sparsity, H_sparsity, W_fixed, H_fixed are read from entry 0; divergence is euclidean or kl (is / ab:
+ * NMFX_ERR_UNSUPPORTED, as are n_gpus > 1, multi_backend != 0 and K_total > 256); tolerance < 0 disables the stop rule; path is ignored.  dtype is the
+ * type of the HOST arrays.  Device arithmetic: V is kept as fp32; W, H, every contraction (v_mfma_f64_16x16x4_f64), update, norm, cost sum and stop
+ * decision are float64, and the stop rule is decided on the device (the host reads the flags every 16 iterations).  A problem's result does not depend
+ * on its place in the batch.  Device memory: 4*m*N (V) + 8*K*N (H) + 16*m*K*batch (W and its transposed copy) + 8*64*KP*(1 kl | 2 euclidean) bytes per
+ * (64 rows, 256 columns) of every problem (KP = K rounded up to 32, 64, 128 or 256) + 8*maxiter*batch, and 8*K*N more for euclidean with K > 128; a
+ * failed allocation is NMFX_ERR_NOMEM with the byte count.
+ * nmfx_last_call_timing describes the call. */
+nmfx_status nmfx_nmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *col_offsets /* batch + 1, col_offsets[0] = 0, increasing */,
+                           nmfx_result *r, int32_t *cost_len /* batch */);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,
