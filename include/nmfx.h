@@ -217,6 +217,17 @@ nmfx_status nmfx_nmf_f64(const nmfx_problem *p, nmfx_result *r);
  * nmfx_last_call_timing describes the call. */
 nmfx_status nmfx_nmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *col_offsets /* batch + 1, col_offsets[0] = 0, increasing */,
                            nmfx_result *r, int32_t *cost_len /* batch */);
+/* `batch` independent cnmf problems (cnmf.m:1, hot loop cnmf.m:175-258) in one call: nmfx_nmf_batch's layouts, arithmetic and rules with p->T = context_len.
+ * The problems share m, K_total, T and the configuration; problem b has n_b = col_offsets[b + 1] - col_offsets[b] >= max(1, T - 1) columns (the reference's
+ * H_shifted, cnmf.m:188, does not exist below T - 1: NMFX_ERR_INVALID).  Result b is what nmfx_cnmf returns for problem b alone.
+ *   p->V  m x N;  p->H_init, r->H  K_total x N;  p->W_init, r->W  m x K_total x T x batch;  r->cost  maxiter x batch, column-major;  cost_len  out [batch]
+ * num_sources must be 1; divergence is euclidean or kl (anything else: NMFX_ERR_UNSUPPORTED, as are n_gpus > 1, multi_backend != 0 and K_total * T > 256);
+ * tolerance < 0 disables the stop rule; path is ignored.  Device arithmetic: V is kept as fp32, everything else is float64 (v_mfma_f64_16x16x4_f64).
+ * Device memory: 4*m*N (V) + 8*K*N (H) + 16*m*K*T*batch (W and its pass operand) + 8*64*KP*(1 kl | 2 euclidean) bytes per (64 rows, 256 columns) of every
+ * problem (KP = K*T rounded up to 32, 64, 128 or 256) + 8*K*T*N*(1 kl | 2 euclidean) (the H-step products) + 8*maxiter*batch; a failed allocation is
+ * NMFX_ERR_NOMEM with the byte count.  nmfx_last_call_timing describes the call. */
+nmfx_status nmfx_cnmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *col_offsets /* batch + 1, col_offsets[0] = 0, increasing */,
+                            nmfx_result *r, int32_t *cost_len /* batch */);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,

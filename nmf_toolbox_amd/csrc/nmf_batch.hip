@@ -9,7 +9,7 @@
 // where the stop rule makes it bite: on the planted problems of tests/test_gpu_nmf_batch.py the rounding of the images (1e-7 per product) is amplified to
 // 4.8e-6 on the cost while the iteration leaves a plateau (euclidean, 96 x 130, iteration 126; measured with a NumPy model of the arithmetic).
 //
-// One kernel (nb_pass) serves both steps, because with both factors stored as rows of K doubles the two steps are the same computation with the roles swapped:
+// One kernel (nb_pass, in nb_pass.h, shared with cnmf_batch.hip: its CONV = false instantiations are this file's) serves both steps, because with both factors stored as rows of K doubles the two steps are the same computation with the roles swapped:
 //     a STATIONARY set of 64 factor rows r (16 per wave, kept in registers as MFMA operands) and a STREAMED set of factor rows c, 64 at a time through LDS;
 //     S(c, r) = sum_k Y(c, k) X(r, k)  (v_mfma_f64_16x16x4_f64), the element map A(c, r) of the divergence on the accumulator registers,
 //     O(k, r) += sum_c Y(c, k) A(c, r): register e of a 16 x 16 block of S is, as it lies, the second operand of step e of that product -- no LDS round trip.
@@ -24,233 +24,10 @@
 //     column: chunk slabs summed in chunk order, the column-sum diag terms, eps guard, unit-L2 column, both copies of W, colsum(W))  ->  nb_pass<H step>.
 // Work items of a problem with done[b] != 0 return at once: its W_b, H_b and cost vector stay as they were when its stop rule fired.  After the last iteration
 // one cost-only W-step pass and one nb_decide close the cost vectors.  The host reads done[] every 16 iterations (only when the stop rule is on) to end early.
-#include "api_common.h"
+#include "nb_pass.h"
 
 namespace nmfx {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr double EPS64 = 2.220446049250313e-16;   // MATLAB's eps, 2^-52
-constexpr int NB_T = 64;                          // tile edge: stationary rows per item, streamed rows per LDS stage
-constexpr int NB_CHUNK = 256;                     // columns of H_b per W-step item
-constexpr int NB_MAX_GRID = 65536;
-enum { NB_EUC = 0, NB_KL = 1 };
-constexpr int nb_ncb(int KP) { return KP == 256 ? 2 : 4; }   // 16-row blocks of the streamed factor per stage: 64 rows, 32 at the widest K (registers: S, A and V per stage)
-
-struct NbProb {
-    long col0;      // first column of the problem in V / H
-    int n;          // its columns
-    int nc, ntr;    // W step: column chunks, row tiles (items witem0 + t*nc + c)
-    int witem0;
-    int hitem0;     // H step: one item per 64 columns
-    int pad_;
-};
-
-__device__ inline double block_sum256(double x, double *sh) {   // deterministic: fixed shuffle tree, then the four waves in order
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
-
-struct NbPass {
-    const NbProb *prob;
-    const int *tab;         // item -> problem
-    int items;
-    const int *done;
-    const float *V;
-    long m;
-    int K;
-    const double *WT;       // [b][i][k]
-    double *Hm;             // [j][k]
-    int cost_only;          // W step: the cost partials only
-    double *slab;           // W step out: [item][which][k][64 rows]
-    double *costpart;       // W step out: [item]
-    const double *cw;       // H step, KL: colsum(W_b) [b][k]
-    double *Pbuf;           // H step, euclidean at the widest K: W_b'*S of the first of its two launches, K x N
-    double lamH;
-};
-
-// WHICH: 0 = everything in one launch.  The euclidean step has two contractions of the second kind (A = V and A = S); at KP = 256 their accumulators alone would
-// be 256 registers per lane next to 128 of stationary operands, so there the step is two launches: 1 = S*Y only (the denominators), 2 = V*Y, the cost and
-// the epilogue (the H step's reads the denominators of launch 1 from Pbuf)
-template <int KP, int DIV, bool HS, int WHICH>
-__global__ __launch_bounds__(256) void nb_pass(const NbPass g) {
-    constexpr int LDY = KP + 4, NKB = KP / 16, NKK = KP / 4;
-    constexpr int NCB = nb_ncb(KP), TS = 16 * NCB;   // streamed rows per LDS stage
-    constexpr bool DO_N = WHICH != 1, DO_P = DIV == NB_EUC && WHICH != 2, COST = !HS && DO_N;
-    constexpr bool NEED_S = DIV == NB_KL || DO_P || COST;
-    static_assert(DIV == NB_EUC || WHICH == 0, "KL has one contraction");
-    extern __shared__ __align__(16) double Ys[];   // [TS][LDY]
-    __shared__ double sh[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;
-    const int K = g.K;
-    const long m = g.m;
-    for (int item = blockIdx.x; item < g.items; item += gridDim.x) {
-        const int b = g.tab[item];
-        if (g.done[b]) continue;   // (uniform) a finished problem is frozen
-        const NbProb pb = g.prob[b];
-        long r0, R, cbeg, cend;
-        const double *X, *Y;
-        if constexpr (!HS) {
-            const int li = item - pb.witem0, t = li / pb.nc, ch = li - t * pb.nc;
-            r0 = (long)t * NB_T; R = m; cbeg = (long)ch * NB_CHUNK; cend = cbeg + NB_CHUNK < pb.n ? cbeg + NB_CHUNK : pb.n;
-            X = g.WT + (long)b * m * K; Y = g.Hm + pb.col0 * K;
-        } else {
-            r0 = (long)(item - pb.hitem0) * NB_T; R = pb.n; cbeg = 0; cend = m;
-            X = g.Hm + pb.col0 * K; Y = g.WT + (long)b * m * K;
-        }
-        const float *Vb = g.V + m * pb.col0;
-        const long r = r0 + 16 * wv + l15;
-        const bool rok = r < R;
-        // the stationary rows as MFMA operands: lane (l15, lg) holds X(r, 4 kk + lg)
-        double xr[NEED_S ? NKK : 1];
-        if constexpr (NEED_S) {
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) {
-                const int k = 4 * kk + lg;
-                xr[kk] = (rok && k < K) ? X[r * K + k] : 0.0;
-            }
-        }
-        f64x4 accN[DO_N ? NKB : 1], accP[DO_P ? NKB : 1];
-#pragma unroll
-        for (int q = 0; q < (DO_N ? NKB : 1); ++q) accN[q] = f64x4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int q = 0; q < (DO_P ? NKB : 1); ++q) accP[q] = f64x4{0.0, 0.0, 0.0, 0.0};
-        double part = 0.0;
-        for (long c0 = cbeg; c0 < cend; c0 += TS) {
-            __syncthreads();   // (the previous stage has been read)
-#pragma unroll 4
-            for (int u = 0; u < TS * KP / 256; ++u) {
-                const int idx = tid + 256 * u, k = idx % KP, c = idx / KP;
-                const long cc = c0 + c;
-                Ys[c * LDY + k] = (cc < cend && k < K) ? Y[cc * K + k] : 0.0;
-            }
-            // this lane's values of V, requested before the first product: block cb, register e <-> streamed row c0 + 16 cb + 4 e + lg, stationary row r
-            f32x4 vv[NCB];
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const long c = c0 + 16 * cb + 4 * e + lg;
-                    const bool ok = rok && c < cend;
-                    vv[cb][e] = ok ? (HS ? Vb[c + m * r] : Vb[r + m * c]) : 1.f;
-                }
-            __syncthreads();
-            f64x4 S[NCB];
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) S[cb] = f64x4{0.0, 0.0, 0.0, 0.0};
-            if constexpr (NEED_S) {
-#pragma unroll
-                for (int kk = 0; kk < NKK; ++kk)
-#pragma unroll
-                    for (int cb = 0; cb < NCB; ++cb)
-                        S[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(Ys[(16 * cb + l15) * LDY + 4 * kk + lg], xr[kk], S[cb], 0, 0, 0);   // S(c = 16 cb + 4 e + lg, r = l15)
-            }
-            // the element map of the divergence, and (W step) the cost terms of the state this pass starts from
-            f64x4 A[NCB];
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const long c = c0 + 16 * cb + 4 * e + lg;
-                    const bool ok = rok && c < cend;
-                    const double s = S[cb][e], v = (double)vv[cb][e];
-                    if constexpr (COST) {
-                        if (ok) {
-                            if constexpr (DIV == NB_EUC) { const double d = v - s; part += d * d; }       // nmf.m:208
-                            else part += (v * log(v / s) - v) + s;                                        // nmf.m:210
-                        }
-                    }
-                    if constexpr (DIV == NB_EUC) { A[cb][e] = ok ? v : 0.0; S[cb][e] = ok ? s : 0.0; }     // nmf.m:149-150,180-181
-                    else A[cb][e] = ok ? v / s : 0.0;                                                      // nmf.m:152,183
-                }
-            if (!g.cost_only) {
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-#pragma unroll
-                        for (int kb = 0; kb < NKB; ++kb) {
-                            const double y = Ys[(16 * cb + 4 * e + lg) * LDY + 16 * kb + l15];
-                            if constexpr (DO_N) accN[kb] = __builtin_amdgcn_mfma_f64_16x16x4f64(y, A[cb][e], accN[kb], 0, 0, 0);   // O(k = 16 kb + 4 e' + lg, r = l15)
-                            if constexpr (DO_P) accP[kb] = __builtin_amdgcn_mfma_f64_16x16x4f64(y, S[cb][e], accP[kb], 0, 0, 0);
-                        }
-            }
-        }
-        if constexpr (!HS) {
-            if (!g.cost_only) {
-                double *sl = g.slab + (long)item * ((DIV == NB_EUC ? 2 : 1) * KP * NB_T) + 16 * wv + l15;
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int k = 16 * kb + 4 * e + lg;
-                        if constexpr (DO_N) sl[k * NB_T] = accN[kb][e];
-                        if constexpr (DO_P) sl[(KP + k) * NB_T] = accP[kb][e];
-                    }
-            }
-            if constexpr (COST) {
-                part = block_sum256(part, sh);
-                if (tid == 0) g.costpart[item] = part;
-            }
-        } else {
-            // nmf.m:199: H .* (neg ./ max(pos + lambda, eps)) on these columns
-            if (rok) {
-                const long base = K * (pb.col0 + r);
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int k = 16 * kb + 4 * e + lg;
-                        if (k >= K) continue;
-                        if constexpr (WHICH == 1) g.Pbuf[base + k] = accP[kb][e];
-                        else {
-                            double pos;
-                            if constexpr (DIV == NB_KL) pos = g.cw[(long)b * K + k];
-                            else if constexpr (WHICH == 2) pos = g.Pbuf[base + k];
-                            else pos = accP[kb][e];
-                            g.Hm[base + k] = g.Hm[base + k] * (accN[kb][e] / fmax(pos + g.lamH, EPS64));
-                        }
-                    }
-            }
-        }
-    }
-}
-
-template <int KP, int DIV, bool HS, int WHICH>
-nmfx_status nb_launch(hipStream_t st, const NbPass &g) {
-    constexpr int lds = 16 * nb_ncb(KP) * (KP + 4) * 8;
-    static LdsAttrOnce attr;
-    TRY(attr.set(reinterpret_cast<const void *>(&nb_pass<KP, DIV, HS, WHICH>), lds));
-    const unsigned grid = (unsigned)std::min(g.items, NB_MAX_GRID);
-    hipLaunchKernelGGL((nb_pass<KP, DIV, HS, WHICH>), dim3(grid), dim3(256), lds, st, g);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
-}
-int nb_kp(int K) { return K <= 32 ? 32 : (K <= 64 ? 64 : (K <= 128 ? 128 : 256)); }
-template <int DIV, bool HS>
-nmfx_status nb_launch_k(hipStream_t st, const NbPass &g) {
-    switch (nb_kp(g.K)) {
-        case 32: return nb_launch<32, DIV, HS, 0>(st, g);
-        case 64: return nb_launch<64, DIV, HS, 0>(st, g);
-        case 128: return nb_launch<128, DIV, HS, 0>(st, g);
-        default:
-            if constexpr (DIV == NB_EUC) {
-                if (!g.cost_only) TRY((nb_launch<256, DIV, HS, 1>(st, g)));
-                return nb_launch<256, DIV, HS, 2>(st, g);
-            } else return nb_launch<256, DIV, HS, 0>(st, g);
-    }
-}
-nmfx_status nb_run_pass(hipStream_t st, const NbPass &g, int div, bool hstep) {
-    if (div == NB_EUC) return hstep ? nb_launch_k<NB_EUC, true>(st, g) : nb_launch_k<NB_EUC, false>(st, g);
-    return hstep ? nb_launch_k<NB_KL, true>(st, g) : nb_launch_k<NB_KL, false>(st, g);
-}
 
 // nmf.m:130-134 for every column of every W_b (fixed or not): unit-L2 columns on the master, the transposed copy, colsum(W) (the KL H-step denominator).
 // A workgroup per (problem, column).  Sum of squares: thread t adds rows t, t + 256, ... in order (fma), then block_sum256
@@ -274,50 +51,6 @@ __global__ __launch_bounds__(256) void nb_wnorm(double *Wm, double *WT, double *
         }
         cs = block_sum256(cs, sh);
         if (threadIdx.x == 0) cw[c] = cs;
-    }
-}
-
-struct NbDecide {
-    const NbProb *prob;
-    int B;
-    int *done;
-    const double *costpart;
-    double *cost;           // [b][maxiter]
-    int maxiter, idx, final;
-    double tol, scale, lamW, lamH;
-    const double *Wm, *Hm;
-    long m;
-    int K;
-};
-// per live problem: cost[idx] = scale * (the W-step pass's partials in item order) + the L1 terms (nmf.m:206-218) of the state that pass saw, then the stop
-// rule (nmf.m:221-224).  done[b] = the length of the problem's cost vector once it is closed (by the rule, or by `final`)
-__global__ __launch_bounds__(256) void nb_decide(const NbDecide g) {
-    __shared__ double sh[4];
-    for (int b = blockIdx.x; b < g.B; b += gridDim.x) {
-        if (g.done[b]) continue;   // (uniform; thread 0 writes done[b] behind the barriers below)
-        const NbProb pb = g.prob[b];
-        const int nit = pb.nc * pb.ntr;
-        double t = 0.0, aw = 0.0, ah = 0.0;
-        for (int q = threadIdx.x; q < nit; q += 256) t += g.costpart[pb.witem0 + q];
-        t = block_sum256(t, sh);
-        if (g.lamW != 0.0) {
-            const double *w = g.Wm + (long)b * g.m * g.K;
-            for (long e = threadIdx.x; e < g.m * g.K; e += 256) aw += fabs(w[e]);
-            aw = block_sum256(aw, sh);
-        }
-        if (g.lamH != 0.0) {
-            const double *h = g.Hm + pb.col0 * g.K;
-            for (long e = threadIdx.x; e < (long)pb.n * g.K; e += 256) ah += fabs(h[e]);
-            ah = block_sum256(ah, sh);
-        }
-        if (threadIdx.x == 0) {
-            double *cv = g.cost + (long)b * g.maxiter;
-            const double c = (g.scale * t + g.lamW * aw) + g.lamH * ah;
-            cv[g.idx] = c;
-            bool stop = g.final != 0;
-            if (!stop && g.tol >= 0 && g.idx >= 1) stop = c < cv[g.idx - 1] && cv[g.idx - 1] - c < g.tol;
-            if (stop) g.done[b] = g.idx + 1;
-        }
     }
 }
 
@@ -387,36 +120,6 @@ __global__ __launch_bounds__(256) void nb_wupdate(const NbWup g) {
         if (threadIdx.x == 0) g.cw[c] = cs;
     }
 }
-
-unsigned grid_of(long count) { return (unsigned)(count < 1 ? 1 : (count > NB_MAX_GRID ? NB_MAX_GRID : count)); }
-
-// host array (p->dtype) -> device doubles: float64 as it is; fp32 through the pinned staging of host_io.hip into `tmp` and widened on the device
-nmfx_status nb_ingest64(hipStream_t st, const void *host, int dtype, double *dev, size_t count, DevBuf &tmp) {
-    if (dtype == NMFX_F64) {
-        NMFX_HIP(hipMemcpyAsync(dev, host, count * 8, hipMemcpyHostToDevice, st));
-        IoStats &io = io_stats();
-        io.h2d_bytes_host += (double)count * 8.0;
-        io.h2d_bytes_pcie += (double)count * 8.0;
-        return NMFX_OK;
-    }
-    TRY(upload(st, host, dtype, tmp.as<float>(), count, 1.0));
-    return cvt_to_f64(st, tmp.as<float>(), dev, (long)count);
-}
-nmfx_status nb_egress64(hipStream_t st, const double *dev, int dtype, void *host, size_t count, DevBuf &tmp) {
-    if (dtype == NMFX_F64) {
-        NMFX_HIP(hipMemcpyAsync(host, dev, count * 8, hipMemcpyDeviceToHost, st));
-        io_stats().d2h_bytes_host += (double)count * 8.0;
-        return NMFX_OK;
-    }
-    TRY(cvt_f64_to_f32(st, dev, tmp.as<float>(), (long)count));
-    return download(st, tmp.as<float>(), dtype, host, count);
-}
-
-struct PooledStream {
-    int dev;
-    hipStream_t st = nullptr;
-    ~PooledStream() { if (st) { (void)hipStreamSynchronize(st); staging_quiesce(); unpool_stream(dev, st); } }
-};
 
 nmfx_status run_nmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *off, nmfx_result *r, int32_t *cost_len) {
     TRY(validate_problem(p, r, false, true));
@@ -497,7 +200,7 @@ nmfx_status run_nmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *o
     hp.tab = dhtab.as<int>(); hp.items = (int)hi;
     NbDecide dd{};
     dd.prob = dprob.as<NbProb>(); dd.B = B; dd.done = ddone.as<int>(); dd.costpart = cpart.as<double>(); dd.cost = dcost.as<double>(); dd.maxiter = maxiter;
-    dd.tol = p->tolerance; dd.scale = div == NB_EUC ? 0.5 : 1.0; dd.lamW = lamW; dd.lamH = lamH; dd.Wm = Wm.as<double>(); dd.Hm = Hm.as<double>(); dd.m = m; dd.K = K;
+    dd.tol = p->tolerance; dd.scale = div == NB_EUC ? 0.5 : 1.0; dd.lamW = lamW; dd.lamH = lamH; dd.Wm = Wm.as<double>(); dd.Hm = Hm.as<double>(); dd.wlen = m * K; dd.K = K;
     NbWup wu{};
     wu.prob = dprob.as<NbProb>(); wu.done = ddone.as<int>(); wu.slab = slab.as<double>(); wu.Wm = Wm.as<double>(); wu.WT = WT.as<double>(); wu.Hm = Hm.as<double>();
     wu.cw = cw.as<double>(); wu.m = m; wu.cols = cols; wu.K = K; wu.KP = KP; wu.euc = div == NB_EUC; wu.lamW = lamW;
@@ -511,7 +214,7 @@ nmfx_status run_nmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *o
     for (int it = 0; it < maxiter; ++it) {
         // the pass that opens iteration it + 1: the W-step sums of (W(it), H(it)) and, from the second iteration on, the cost of iteration it
         wp.cost_only = fixW;
-        if (!fixW || it > 0) TRY(nb_run_pass(st, wp, div, false));
+        if (!fixW || it > 0) TRY(nb_run_pass<false>(st, wp, div, false));
         if (it > 0) {
             TRY(decide(it - 1, 0));
             if (p->tolerance >= 0 && it % 16 == 0) {   // nobody left to iterate?
@@ -525,11 +228,11 @@ nmfx_status run_nmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *o
             hipLaunchKernelGGL(nb_wupdate, dim3(grid_of(cols)), dim3(256), 0, st, wu);
             NMFX_HIP(hipGetLastError());
         }
-        if (!fixH) TRY(nb_run_pass(st, hp, div, true));
+        if (!fixH) TRY(nb_run_pass<false>(st, hp, div, true));
     }
     if (!all_done) {   // nmf.m:203-218 of the last iteration, for the problems still running
         wp.cost_only = 1;
-        TRY(nb_run_pass(st, wp, div, false));
+        TRY(nb_run_pass<false>(st, wp, div, false));
         TRY(decide(maxiter - 1, 1));
     }
     NMFX_HIP(hipMemcpyAsync(hdone.data(), ddone.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
