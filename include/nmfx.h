@@ -198,6 +198,18 @@ nmfx_status nmfx_seminmf(const nmfx_problem *p, nmfx_result *r);
  * reads 8 bytes per iteration when tolerance >= 0).  A failed device allocation is NMFX_ERR_NOMEM with the byte count in the message: the call holds
  * 8*m*n*(1 euclidean | 2 kl | 3 is, ab) bytes plus O((m + n)*K).  nmfx_last_call_timing describes it. */
 nmfx_status nmfx_nmf_f64(const nmfx_problem *p, nmfx_result *r);
+/* [W,H,cost] = weighted nmf: nmf.m:1 (hot loop nmf.m:143-225) with every element of the data fit weighted by M (m x n, p->dtype, column-major, >= 0),
+ * for missing or unreliable entries of V.  With S = W*H the mapped operands are A = M.*V, B = M.*S (euclidean), A = M.*V./S, B = M (kl), A = M.*V./S.^2,
+ * B = M./S (is); the W step contracts N = A*H', P = B*H' (with the reference's diag(diag(.)) terms as column sums of W.*P and W.*N), the H step W'*A and
+ * W'*B, and cost = sum(M.*d(V, S)) + the L1 terms.  Where M == 0 an element contributes exactly 0 and V is never looked at there (it may be NaN, Inf or
+ * negative); where M > 0 the expressions are nmfx_nmf's, and with M == 1 everywhere the call computes what nmfx_nmf computes.  A new entry point; no
+ * structure grows, so NMFX_VERSION stays 600.  Every field means what it means for nmfx_nmf (several sources; sparsities; fixed factors; maxiter;
+ * tolerance, < 0 disables the stop rule; device), except: path is ignored (there is one path), NMFX_DIV_AB, T != 1, n_gpus > 1 and multi_backend != 0 are
+ * NMFX_ERR_UNSUPPORTED, and a NULL M is NMFX_ERR_INVALID.  W_init is normalised to unit L2 columns for every source (nmf.m:130-134).  result.cost needs
+ * maxiter entries and is trimmed by the stop rule like nmf's (the host reads 8 bytes per iteration when tolerance >= 0).  A failed device allocation is
+ * NMFX_ERR_NOMEM with the byte count in the message: the call holds 4*m*n*(3 kl | 4 euclidean, is) bytes (V, M and the mapped operands as fp32) plus
+ * O((m + n)*K).  nmfx_last_call_timing describes it. */
+nmfx_status nmfx_wnmf(const nmfx_problem *p, const void *M, nmfx_result *r);
 /* `batch` independent nmf problems (nmf.m:1, hot loop nmf.m:143-225) in one call: they share m, K_total and the configuration, problem b has its own
  * n_b = col_offsets[b + 1] - col_offsets[b] >= 1 columns, its own W_b, H_b, cost vector and stopping point.  Result b is what nmfx_nmf returns for problem b
  * alone; a problem whose stop rule fires at iteration t keeps W(t), H(t) and a cost vector of length t while the others run on.  A new entry point; no

@@ -1,0 +1,371 @@
+// Weighted NMF: nmfx_wnmf.  nmf.m:143-225 with every element of the data fit weighted by M >= 0 (m x n, the shape of V); S = W*H:
+//     divergence   A             B        d(V, S)
+//     euclidean    M.*V          M.*S     0.5*(V - S).^2
+//     kl           M.*V./S       M        V.*log(V./S) - V + S
+//     is           M.*V./S.^2    M./S     log(S./V) + V./S - 1
+//   W step:  N = A*H', P = B*H', neg = N + W.*cs(W.*P), pos = P + W.*cs(W.*N) (cs = column sums: the reference's diag(diag(.)) terms),
+//            W <- W.*(neg ./ max(pos + lambda_W, eps)), unit-L2 columns                                  (nmf.m:148-169)
+//   H step:  H <- H.*((W'*A) ./ max(W'*B + lambda_H, eps)) with S from the new W                         (nmf.m:178-199)
+//   cost(t) = sum(M.*d(V, S)) + the L1 terms after the H step; stop rule nmf.m:221
+// With weights neither shortcut of the unweighted paths holds: the KL denominators are M*H' and W'*M instead of row and column sums, and the euclidean Gram
+// forms W*(H*H'), (W'*W)*H are no longer V_hat*H', W'*V_hat.  Both maps of S are needed element by element.
+//
+// Device state (column-major): V and M as fp32; W and H as float64 masters with fp32 images (the operands of the MFMA passes), as everywhere in the library;
+// the mapped operands A and B as fp32 m x n.  The constant ones are formed once per call (M.*V for euclidean; for kl B is M itself), so the call holds
+// 4*m*n*(3 kl | 4 euclidean, is) bytes plus O((m + n)*K).
+//
+// The weighted map pass (wmap_kernel): one workgroup owns a 128 x 64 tile of S, accumulated on v_mfma_f32_32x32x2_f32 over any K >= 1 (both factors staged
+// through LDS 16 k at a time, two buffers, the next stage in flight in registers; the K tail is zero-filled in LDS, nothing is padded in HBM).  Each of the
+// four waves holds 32 rows x 64 columns = two accumulator blocks.  The MFMA is fed transposed (first operand H', second W): the 32 lanes of a result register
+// then run along i, the contiguous dimension of V, M, A and B, so every epilogue access is a 128-byte line per half wave.  The lane's values of V and M are
+// requested behind the first stage and arrive under the contraction.  The divergence's map and whether the pass stores, sums the cost, or both are template
+// parameters.  Where M == 0 the maps SELECT zero: V is never looked at there (it is also zeroed at ingest), so 0*NaN cannot occur; where M > 0 the expressions
+// are nmf's.  A and B are formed in fp32 with IEEE division; the cost terms in float64 from the fp32 S, V and M (a well-fitting element's term is a
+// difference of quantities of the size of V: in fp32 its rounding alone is 1e-7*V against a term of V*(1 - V/S)^2/2).  Every workgroup adds the terms of the
+// tiles it walks in a fixed order and writes ONE float64 partial; finish_cost adds the partials in index order: no atomics, run to run identical.
+// LDS: W stage [16][128] floats (a half wave reads 32 consecutive floats: no conflict), H stage [64][17] (row stride 17 words: 32 rows on 32 distinct banks).
+// (The bank arguments are reasoning from the LDS bank layout, not measured.)
+//
+// Second products A*H', B*H', W'*A, W'*B: the library's pipelined fp32 GEMM (gemm_auto, slabs over the long contraction when the output is small).
+// Schedule (nmf64's): the cost of iteration t is the by-product of the first map pass of iteration t + 1, plus one cost-only pass after the last iteration;
+// with the stop rule on, the host reads those 8 bytes BEFORE the W update of t + 1 is launched, so a stop returns W(t), H(t) without a spare copy.
+#include "api_common.h"
+#include "gemm_common.h"
+
+namespace nmfx {
+namespace {
+
+enum WMap { WM_EUC = 0, WM_KL = 1, WM_IS = 2 };
+
+constexpr int WBM = 128, WBN = 64, WBK = 16, WLDH = WBK + 1;
+constexpr int WMAP_MAX_GRID = 8192;
+
+struct WMapArgs {
+    const float *W, *H;     // fp32 images: W[i + m*k], H[k + K*j]
+    const float *V, *M;     // m x n
+    float *A, *B;           // m x n outputs of a storing pass (either may be NULL: not needed by the divergence)
+    long m, n;
+    int K;
+    double *partials;       // [gridDim.x] weighted data-fit partials of a cost pass
+};
+
+__device__ inline double wblock_sum256(double x, double *sh) {   // deterministic: fixed shuffle tree, then the four waves in order
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+    __syncthreads();
+    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    __syncthreads();
+    return r;
+}
+
+template <int MAP, bool STORE, bool COST>
+__global__ __launch_bounds__(256, 2) void wmap_kernel(const WMapArgs g) {
+    constexpr bool NEED_V = COST || MAP != WM_EUC;   // the storing euclidean pass forms B = M.*S only
+    __shared__ float Ws[2][WBK * WBM];
+    __shared__ float Hs[2][WBN * WLDH];
+    __shared__ double sh[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lh = lane >> 5;
+    const long tilesM = (g.m + WBM - 1) / WBM, tilesN = (g.n + WBN - 1) / WBN, tiles = tilesM * tilesN;
+    const int K = g.K, nk = (K + WBK - 1) / WBK;
+    // loaders: consecutive threads along the operand's contiguous dimension (W: i, H: k)
+    const int w_r = tid & (WBM - 1), w_k = tid >> 7;      // + 2 u, u < 8
+    const int h_k = tid & (WBK - 1), h_c = tid >> 4;      // + 16 u, u < 4
+    double part = 0.0;
+    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long i0 = (t % tilesM) * WBM, j0 = (t / tilesM) * WBN;
+        float rw[8], rh[4];
+        auto gload = [&](int k0) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const long i = i0 + w_r;
+                const int k = k0 + w_k + 2 * u;
+                rw[u] = (i < g.m && k < K) ? g.W[i + g.m * k] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const long j = j0 + h_c + 16 * u;
+                const int k = k0 + h_k;
+                rh[u] = (j < g.n && k < K) ? g.H[k + (long)K * j] : 0.0f;
+            }
+        };
+        auto lstore = [&](int buf) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) Ws[buf][(w_k + 2 * u) * WBM + w_r] = rw[u];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) Hs[buf][(h_c + 16 * u) * WLDH + h_k] = rh[u];
+        };
+        f32x16 acc[2];
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[y][e] = 0.0f;
+        gload(0);
+        lstore(0);
+        // this lane's elements of M (and V), requested behind the first stage: they arrive under the contraction.
+        // acc[y][e]: column (lane & 31) -> i, row (e & 3) + 8 (e >> 2) + 4 (lane >> 5) -> j
+        // (An element outside the matrix reads the clamped address of one inside instead of a guarded load: 32 live predicates are 64 scalar registers.  The
+        // epilogue skips those elements.)
+        const long i = i0 + 32 * wv + l31, ic = i < g.m ? i : g.m - 1;
+        f32x16 vreg[2], mreg[2];
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const long j = j0 + 32 * y + (e & 3) + 8 * (e >> 2) + 4 * lh, jc = j < g.n ? j : g.n - 1;
+                mreg[y][e] = g.M[ic + g.m * jc];
+                vreg[y][e] = NEED_V ? g.V[ic + g.m * jc] : 0.0f;
+            }
+        __builtin_amdgcn_sched_barrier(0);   // (or the compiler sinks every one of them to its first use)
+        __syncthreads();
+        for (int kt = 0; kt < nk; ++kt) {
+            const int buf = kt & 1;
+            if (kt + 1 < nk) gload((kt + 1) * WBK);
+            const float *a = Ws[buf], *b = Hs[buf];
+#pragma unroll
+            for (int kk = 0; kk < WBK / 2; ++kk) {
+                const int k = 2 * kk + lh;
+                const float wf = a[k * WBM + 32 * wv + l31];
+#pragma unroll
+                for (int y = 0; y < 2; ++y) {
+                    const float hf = b[(32 * y + l31) * WLDH + k];
+                    acc[y] = __builtin_amdgcn_mfma_f32_32x32x2f32(hf, wf, acc[y], 0, 0, 0);   // D(row = j, col = i)
+                }
+            }
+            if (kt + 1 < nk) lstore(buf ^ 1);   // (the other buffer: last read one trip ago, behind the barrier below)
+            __syncthreads();
+        }
+        // The element map, the float64 logarithm of a cost pass most of all, is long: unrolled over the 32 results of a lane the kernel runs out of registers.
+        // The loop over the two accumulator blocks stays rolled; a rolled loop cannot index registers, so the second block moves into the first one's place.
+#pragma unroll 1
+        for (int y = 0; y < 2; ++y) {
+            const f32x16 s16 = acc[0], v16 = vreg[0], m16 = mreg[0];
+            acc[0] = acc[1]; vreg[0] = vreg[1]; mreg[0] = mreg[1];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const long j = j0 + 32 * y + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                const float s = s16[e], v = v16[e], w = m16[e];
+                const bool on = w > 0.0f && i < g.m && j < g.n;
+                const long idx = i + g.m * j;
+                if constexpr (STORE) {
+                    if (i < g.m && j < g.n) {
+                        if constexpr (MAP == WM_EUC) g.B[idx] = on ? w * s : 0.0f;
+                        else if constexpr (MAP == WM_KL) g.A[idx] = on ? (w * v) / s : 0.0f;            // nmf.m:152
+                        else { g.A[idx] = on ? (w * v) / (s * s) : 0.0f; g.B[idx] = on ? w / s : 0.0f; }   // nmf.m:155-156
+                    }
+                }
+                if constexpr (COST) {
+                    const double sd = (double)s, vd = (double)v;
+                    double c;
+                    if constexpr (MAP == WM_EUC) { const double d = vd - sd; c = d * d; }              // nmf.m:208 (0.5 applied to the sum)
+                    else if constexpr (MAP == WM_KL) c = (vd * log(vd / sd) - vd) + sd;                 // nmf.m:210
+                    else c = (log(sd / vd) + vd / sd) - 1.0;                                            // nmf.m:212
+                    part += on ? (double)w * c : 0.0;
+                }
+            }
+        }
+    }
+    if constexpr (COST) {
+        part = wblock_sum256(part, sh);
+        if (tid == 0) g.partials[blockIdx.x] = part;
+    }
+}
+
+long wmap_grid(long m, long n) { return std::min<long>(((m + WBM - 1) / WBM) * ((n + WBN - 1) / WBN), WMAP_MAX_GRID); }
+
+template <int MAP>
+nmfx_status wmap_launch(hipStream_t st, const WMapArgs &g, bool store, bool cost) {
+    const dim3 grid((unsigned)wmap_grid(g.m, g.n)), block(256);
+    if (store && cost) hipLaunchKernelGGL((wmap_kernel<MAP, true, true>), grid, block, 0, st, g);
+    else if (store) hipLaunchKernelGGL((wmap_kernel<MAP, true, false>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL((wmap_kernel<MAP, false, true>), grid, block, 0, st, g);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+// ingest: V <- 0 where M == 0 (whatever was there: NaN, Inf, negative), and the constant operand M.*V of the euclidean maps
+__global__ __launch_bounds__(256) void wnmf_prepare(float *V, const float *M, float *MV, long count) {
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < count; e += (long)gridDim.x * 256) {
+        const float w = M[e];
+        const bool on = w > 0.0f;
+        const float v = on ? V[e] : 0.0f;
+        if (!on) V[e] = 0.0f;
+        if (MV) MV[e] = on ? w * v : 0.0f;
+    }
+}
+unsigned grid1(long count) { const long b = (count + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b)); }
+
+// host factor (p->dtype) -> float64 master + fp32 image
+nmfx_status ingest_factor(hipStream_t st, const void *host, int dtype, double *d64, float *d32, size_t count) {
+    if (dtype == NMFX_F64) {
+        NMFX_HIP(hipMemcpyAsync(d64, host, count * 8, hipMemcpyHostToDevice, st));
+        IoStats &io = io_stats();
+        io.h2d_bytes_host += (double)count * 8.0;
+        io.h2d_bytes_pcie += (double)count * 8.0;
+        return cvt_f64_to_f32(st, d64, d32, (long)count);
+    }
+    TRY(upload(st, host, dtype, d32, count, 1.0));
+    return cvt_to_f64(st, d32, d64, (long)count);
+}
+nmfx_status egress_factor(hipStream_t st, const double *d64, const float *d32, int dtype, void *host, size_t count) {
+    if (dtype == NMFX_F64) {
+        NMFX_HIP(hipMemcpyAsync(host, d64, count * 8, hipMemcpyDeviceToHost, st));
+        io_stats().d2h_bytes_host += (double)count * 8.0;
+        return NMFX_OK;
+    }
+    return download(st, d32, dtype, host, count);
+}
+
+nmfx_status run_wnmf(const nmfx_problem *p, const void *Mhost, nmfx_result *r) {
+    TRY(validate_problem(p, r, false, true));
+    if (!Mhost) { set_error("wnmf: the weight matrix M is required"); return NMFX_ERR_INVALID; }
+    if (p->T != 1) { set_error("wnmf: T must be 1"); return NMFX_ERR_UNSUPPORTED; }
+    if (p->n_gpus > 1 || p->multi_backend != 0) { set_error("wnmf: one GPU only (n_gpus = %d, multi_backend = %d)", p->n_gpus, p->multi_backend); return NMFX_ERR_UNSUPPORTED; }
+    int map;
+    switch (p->divergence) {
+        case NMFX_DIV_EUCLIDEAN: map = WM_EUC; break;
+        case NMFX_DIV_KL: map = WM_KL; break;
+        case NMFX_DIV_IS: map = WM_IS; break;
+        case NMFX_DIV_AB: set_error("wnmf: the alpha-beta divergence is not supported (euclidean, kl, is)"); return NMFX_ERR_UNSUPPORTED;
+        default: set_error("wnmf: divergence %d has no update equations (nmf.m:165-166)", p->divergence); return NMFX_ERR_INVALID;
+    }
+    DeviceGuard dg_;
+    TRY(check_device(p->n_gpus == 1 && p->device_ids ? p->device_ids[0] : p->device));
+    const long m = p->m, n = p->n;
+    const int K = p->K_total, S = p->num_sources;
+    const size_t mn = (size_t)m * n, mK = (size_t)m * K, Kn = (size_t)K * n;
+    std::vector<float> lw(K, 0.0f), lh(K, 0.0f);
+    std::vector<uint8_t> fw(K, 0), fh(K, 0);
+    bool all_wf = true, all_hf = true, any_lw = false, any_lh = false;
+    for (int s = 0, k = 0; s < S; ++s) {
+        const int ks = p->K_s ? p->K_s[s] : K;
+        for (int q = 0; q < ks; ++q, ++k) {
+            lw[k] = (float)(p->W_sparsity ? p->W_sparsity[s] : 0.0);
+            lh[k] = (float)(p->H_sparsity ? p->H_sparsity[s] : 0.0);
+            fw[k] = p->W_fixed ? (p->W_fixed[s] != 0) : 0;
+            fh[k] = p->H_fixed ? (p->H_fixed[s] != 0) : 0;
+            all_wf = all_wf && fw[k];
+            all_hf = all_hf && fh[k];
+            any_lw = any_lw || lw[k] != 0.0f;
+            any_lh = any_lh || lh[k] != 0.0f;
+        }
+    }
+    const bool own_b = map != WM_KL;   // euclidean: A = M.*V (constant), B per pass; kl: A per pass, B = M itself; is: both per pass
+    const size_t gscratch = std::max(gemm_scratch_bytes(m, K, n), gemm_scratch_bytes(K, n, m));
+    const long np = wmap_grid(m, n);
+    DevBuf Vd, Md, Ad, Bd, W64d, H64d, W32d, H32d, Nw, Pw, Nh, Ph, scr, parts, vecs, lamd, fixd, dcost, rrs;
+    TRY(Vd.alloc(mn * 4)); TRY(Md.alloc(mn * 4));
+    TRY(Ad.alloc(mn * 4));
+    if (own_b) TRY(Bd.alloc(mn * 4));
+    TRY(W64d.alloc(mK * 8)); TRY(H64d.alloc(Kn * 8)); TRY(W32d.alloc(mK * 4)); TRY(H32d.alloc(Kn * 4));
+    TRY(Nw.alloc(mK * 4)); TRY(Pw.alloc(mK * 4)); TRY(Nh.alloc(Kn * 4)); TRY(Ph.alloc(Kn * 4));
+    TRY(scr.alloc(gscratch)); TRY(parts.alloc((size_t)np * 8)); TRY(vecs.alloc((size_t)3 * K * 8));
+    TRY(lamd.alloc((size_t)2 * K * 4)); TRY(fixd.alloc((size_t)2 * K)); TRY(dcost.alloc((size_t)p->maxiter * 8));
+    TRY(rrs.alloc(row_reduce_scratch_bytes(K)));
+    float *V = Vd.as<float>(), *M = Md.as<float>(), *A = Ad.as<float>(), *B = own_b ? Bd.as<float>() : M;
+    double *W64 = W64d.as<double>(), *H64 = H64d.as<double>();
+    float *W = W32d.as<float>(), *H = H32d.as<float>();
+    double *sumsq = vecs.as<double>(), *l1W = sumsq + K, *l1H = sumsq + 2 * K;
+    float *lamW = lamd.as<float>(), *lamH = lamW + K;
+    uint8_t *fixW = fixd.as<uint8_t>(), *fixH = fixW + K;
+    hipStream_t st = nullptr;
+    StreamDrain drain_(st);
+    CallClock clock;
+    NMFX_HIP(hipMemcpyAsync(lamW, lw.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(lamH, lh.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(fixW, fw.data(), (size_t)K, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(fixH, fh.data(), (size_t)K, hipMemcpyHostToDevice, st));
+    TRY(upload(st, p->V, p->dtype, V, mn, 1.0));
+    TRY(upload(st, Mhost, p->dtype, M, mn, 1.0));
+    TRY(ingest_factor(st, p->W_init, p->dtype, W64, W, mK));
+    TRY(ingest_factor(st, p->H_init, p->dtype, H64, H, Kn));
+    hipLaunchKernelGGL(wnmf_prepare, dim3(grid1((long)mn)), dim3(256), 0, st, V, M, map == WM_EUC ? A : nullptr, (long)mn);
+    NMFX_HIP(hipGetLastError());
+    NMFX_HIP(hipStreamSynchronize(st));   // (the caller's pageable buffers and the host vectors above have been read)
+    clock.end(&IoStats::ingest_s);
+
+    TRY(col_reduce64(st, W64, m, m, K, 1, sumsq));                                    // nmf.m:130-134: every source, fixed ones included
+    TRY(w_normalize(st, W, m, K, 1, sumsq, nullptr, 0, nullptr, 0, W64));
+    // S = W*H in registers -> the mapped operands and / or the weighted data-fit partials of the current (W, H)
+    auto s_map = [&](bool store, bool cost) -> nmfx_status {
+        WMapArgs g{};
+        g.W = W; g.H = H; g.V = V; g.M = M; g.m = m; g.n = n; g.K = K;
+        g.A = map == WM_EUC ? nullptr : A; g.B = map == WM_KL ? nullptr : B;
+        g.partials = parts.as<double>();
+        switch (map) {
+            case WM_EUC: return wmap_launch<WM_EUC>(st, g, store, cost);
+            case WM_KL: return wmap_launch<WM_KL>(st, g, store, cost);
+            default: return wmap_launch<WM_IS>(st, g, store, cost);
+        }
+    };
+    auto cost_of_pass = [&](int idx) -> nmfx_status {   // cost[idx] of the state the last s_map(., true) saw (nmf.m:206-218)
+        if (any_lw) TRY(col_reduce(st, W, m, m, K, 2, l1W));
+        if (any_lh) TRY(row_reduce(st, H, K, K, n, 2, l1H, rrs.p));
+        return finish_cost(st, parts.as<double>(), (int)np, map == WM_EUC ? 0.5 : 1.0, any_lw ? l1W : nullptr, K, lamW, any_lh ? l1H : nullptr, K, lamH,
+                           dcost.as<double>() + idx);
+    };
+    auto product = [&](long Mo, long No, long Kc, OpView a, OpView b, float *C) -> nmfx_status {
+        GemmParams g;
+        memset(&g, 0, sizeof(g));
+        g.M = Mo; g.N = No; g.Kc = Kc; g.A = a; g.B = b; g.C = C; g.ldc = Mo; g.epi = EPI_STORE; g.splitk = 1;
+        return gemm_auto(st, g, scr.p, gscratch);
+    };
+    const OpView h_rc{H, nullptr, (long)K, VIEW_RC, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f}, w_kc{W, nullptr, m, VIEW_KC, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f};
+    auto w_step = [&]() -> nmfx_status {
+        TRY(product(m, K, n, OpView{A, nullptr, m, VIEW_RC, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f}, h_rc, Nw.as<float>()));   // N = A*H'
+        TRY(product(m, K, n, OpView{B, nullptr, m, VIEW_RC, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f}, h_rc, Pw.as<float>()));   // P = B*H'
+        WUpdateParams u{};
+        u.W = W; u.W64 = W64; u.N = Nw.as<float>(); u.P = Pw.as<float>(); u.lamW = lamW; u.fixW = fixW; u.m = m; u.K = K; u.T = 1;
+        u.sumsq = sumsq; u.inv_exp = 1.0f; u.rule = 0; u.n_chunks = 1; u.fuse_norm = 1;   // nmf.m:168-169 in double on the master, both arrays written
+        return w_update(st, u);
+    };
+    auto h_step = [&]() -> nmfx_status {
+        TRY(product(K, n, m, w_kc, OpView{A, nullptr, m, VIEW_KC, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f}, Nh.as<float>()));   // W'*A
+        TRY(product(K, n, m, w_kc, OpView{B, nullptr, m, VIEW_KC, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f}, Ph.as<float>()));   // W'*B
+        return h_update(st, H, Nh.as<float>(), Ph.as<float>(), nullptr, K, n, lamH, fixH, 1.0f, 1, 0, H64);              // nmf.m:199 in double on the master
+    };
+    int it = 0;
+    bool stopped = false;
+    for (; it < p->maxiter; ++it) {
+        // the pass that opens iteration it + 1: the mapped operands of (W(it), H(it)) and, from the second iteration on, the cost of iteration it
+        bool maps_current = false;
+        if (it > 0 || !all_wf) {
+            const bool store = !all_wf || !all_hf;
+            TRY(s_map(store, it > 0));
+            maps_current = store;
+        }
+        if (it > 0) {
+            TRY(cost_of_pass(it - 1));
+            if (p->tolerance >= 0) {
+                NMFX_HIP(hipMemcpy(&r->cost[it - 1], dcost.as<double>() + (it - 1), 8, hipMemcpyDeviceToHost));
+                if (mu_stop(0, r->cost, it - 1, p->tolerance)) { stopped = true; break; }   // nmf.m:221-224: W(it), H(it) are still in place
+            }
+        }
+        if (!all_wf) {
+            TRY(w_step());
+            maps_current = false;
+        }
+        if (!all_hf) {
+            if (!maps_current) TRY(s_map(true, false));   // nmf.m:173: the H step sees W's new columns
+            TRY(h_step());
+        }
+    }
+    if (!stopped) {   // nmf.m:203-218 of the last iteration: the cost-only form
+        TRY(s_map(false, true));
+        TRY(cost_of_pass(p->maxiter - 1));
+    }
+    NMFX_HIP(hipMemcpy(r->cost, dcost.p, (size_t)it * 8, hipMemcpyDeviceToHost));
+    r->cost_len = r->iters_run = it;
+    clock.end(&IoStats::iterate_s);
+    TRY(egress_factor(st, W64, W, p->dtype, r->W, mK));
+    NMFX_HIP(hipStreamSynchronize(st));
+    TRY(egress_factor(st, H64, H, p->dtype, r->H, Kn));
+    NMFX_HIP(hipStreamSynchronize(st));
+    clock.end(&IoStats::egress_s);
+    return NMFX_OK;
+}
+
+}  // namespace
+}  // namespace nmfx
+
+extern "C" nmfx_status nmfx_wnmf(const nmfx_problem *p, const void *M, nmfx_result *r) { return nmfx::run_wnmf(p, M, r); }

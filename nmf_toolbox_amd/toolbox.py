@@ -13,6 +13,7 @@
     W, H, cost = seminmf(V, num_basis_elems, config)              seminmf.m:1         (mixed-sign V, k-means default H_init)
     W, H, cost = nmf_batch(Vs, num_basis_elems, config)           nmf.m:1 per problem (lists: B independent problems in one call)
     W, H, cost = cnmf_batch(Vs, num_basis_elems, context_len, config)   cnmf.m:1 per problem (lists: B independent problems in one call)
+    W, H, cost = wnmf(V, M, num_basis_elems, config)              nmf.m:1 with per-entry weights M >= 0 (missing or unreliable data)
 
 Same argument meaning, defaults and error behaviour as the MATLAB functions (a MATLAB cell array is
 a Python list, a struct a dict; errors are ValueError carrying the reference's message).  This file
@@ -173,7 +174,7 @@ def _f_order(a, dtype):
     return a if (a.dtype == dtype and a.flags.f_contiguous) else np.asfortranarray(a, dtype=dtype)
 
 
-def _run_mu(fn, V, Ks, T, cfg, W, H, divergence, device):
+def _run_mu(fn, V, Ks, T, cfg, W, H, divergence, device, extra=()):
     m, n = V.shape
     S = len(Ks)
     K = int(sum(Ks))
@@ -218,7 +219,7 @@ def _run_mu(fn, V, Ks, T, cfg, W, H, divergence, device):
     p.multi_backend = _multi_backend(cfg.get("nmfx_multi_backend", None))
     r = _lib.Result()
     r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
-    _lib.check(fn(C.byref(p), C.byref(r)))
+    _lib.check(fn(C.byref(p), *extra, C.byref(r)))     # (extra: what an entry point takes between the problem and the result -- wnmf's weights)
     cost = cost[: r.cost_len].copy()
     Wl, Hl, k0 = [], [], 0
     for s in range(S):
@@ -251,6 +252,63 @@ def nmf(V, num_basis_elems, config=None, device=0):
     Wl, Hl, cost = _run_mu(lib.nmfx_nmf_f64 if f64 else lib.nmfx_nmf, V, Ks, 1, cfg, W, H, _DIV_NMF[div], device)
     Wl = [w[:, :, 0] for w in Wl]
     return (Wl if is_W_cell else Wl[0]), (Hl if is_H_cell else Hl[0]), cost                        # nmf.m:228-234
+
+
+_DIV_WNMF = {"euclidean": _lib.DIV_EUCLIDEAN, "kl_divergence": _lib.DIV_KL, "kl": _lib.DIV_KL, "is_divergence": _lib.DIV_IS, "is": _lib.DIV_IS}
+
+
+def wnmf(V, M, num_basis_elems, config=None, device=0):
+    """W, H, cost = wnmf(V, M, num_basis_elems, config): weighted NMF -- nmf (nmf.m:1) with every element of the data fit weighted by M >= 0, for
+    missing or unreliable entries of V.  With S = W*H:
+
+        divergence        A             B        d(V, S)
+        'euclidean'       M.*V          M.*S     0.5*(V - S).^2
+        'kl'              M.*V./S       M        V.*log(V./S) - V + S
+        'is'              M.*V./S.^2    M./S     log(S./V) + V./S - 1
+
+    the W step contracts A*H' and B*H' (nmf.m:148-169 with these operands, unit-L2 columns), the H step W'*A and W'*B (nmf.m:178-199), and
+    cost = sum(M.*d(V, S)) + the sparsity terms; the stop rule is nmf's.  Where M == 0 the entry contributes exactly nothing and V is never looked at
+    there: it may be NaN, Inf or negative.  With M == 1 everywhere the result is nmf's.
+
+    M has the shape of V; bool, integer or float; it travels in V's dtype (float32 stays float32, anything else is float64, as for nmf).  A weight that
+    is negative or not finite is a ValueError.  num_basis_elems and config are nmf's (several sources as lists; W_init, H_init, sparsities, fixed
+    factors, maxiter, tolerance, seed: the defaults and the arrays drawn are nmf's), with divergence 'euclidean', 'kl' / 'kl_divergence' or
+    'is' / 'is_divergence'.  One GPU and fp32 device arithmetic with float64 master copies of W and H: nmfx_gpus, nmfx_multi_backend and
+    nmfx_precision='float64' are refused, nmfx_path is ignored (there is one path)."""
+    cfg0 = config if config else {}
+    try:
+        _precision(cfg0, "wnmf")     # (raises for 'float64' / 'double' -- nothing runs silently in another precision -- and for invalid values)
+    except ValueError as e:
+        raise ValueError(str(e) if "wnmf" in str(e) else "wnmf: " + str(e)) from None
+    if cfg0.get("nmfx_gpus", None) is not None or cfg0.get("nmfx_multi_backend", None) is not None:
+        raise ValueError("wnmf runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported")
+    div = cfg0.get("divergence", "euclidean")
+    if div in ("ab_divergence", "ab"):
+        raise ValueError("wnmf has no alpha-beta divergence: its divergences are 'euclidean', 'kl' ('kl_divergence') and 'is' ('is_divergence')")
+    if not isinstance(div, str) or div not in _DIV_WNMF:
+        raise ValueError("wnmf: no update equations defined for cost function with divergence type " + str(div))
+    V = _as_data(V)
+    if V.ndim != 2:
+        raise ValueError("wnmf: V must be a matrix")
+    M = np.asarray(M)
+    if M.shape != V.shape:
+        raise ValueError("wnmf: M must have the shape of V, %r; got %r" % (V.shape, M.shape))
+    if M.dtype.kind not in "buif":
+        raise ValueError("wnmf: M must be bool, integer or float; got %s" % M.dtype)
+    if M.dtype.kind == "f" and not np.all(np.isfinite(M)):
+        raise ValueError("wnmf: every weight in M must be finite")
+    if M.dtype.kind in "if" and M.size and M.min() < 0:
+        raise ValueError("wnmf: every weight in M must be >= 0")
+    with np.errstate(over="ignore"):     # (a float64 weight beyond float32's range becomes Inf and is refused below)
+        Mf = _f_order(M, V.dtype)
+    if not np.all(np.isfinite(Mf)):
+        raise ValueError("wnmf: every weight in M must be finite in V's dtype (%s)" % V.dtype)
+    Ks = [int(k) for k in (num_basis_elems if _is_cell(num_basis_elems) else [num_basis_elems])]   # nmf.m:114-117
+    cfg, W, H, is_W_cell, is_H_cell = _validate(V, Ks, 1, config, False)                           # nmf.m:118
+    lib = _lib.load()
+    Wl, Hl, cost = _run_mu(lib.nmfx_wnmf, V, Ks, 1, cfg, W, H, _DIV_WNMF[div], device, extra=(_fptr(Mf),))
+    Wl = [w[:, :, 0] for w in Wl]
+    return (Wl if is_W_cell else Wl[0]), (Hl if is_H_cell else Hl[0]), cost
 
 
 _DIV_BATCH = {"euclidean": _lib.DIV_EUCLIDEAN, "kl_divergence": _lib.DIV_KL, "kl": _lib.DIV_KL}
