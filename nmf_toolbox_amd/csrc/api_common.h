@@ -1,5 +1,7 @@
 // Shared by every translation unit behind the C ABI (the engine, the host staging, the blocking drivers of each algorithm, the RCCL backend): device guard,
 // workspace carver, hipEvent profiler, the engine object, host <-> device staging, and the scaffolding of a blocking call (devices and shard bounds, stop rule, call clock).
+// Also the host-side leaf helpers of the single-GPU add-on drivers: grid1, single_gpu_device, expand_sources, the float64 staging.  Their one
+// device-side helper, block_sum256, is dev_reduce.h's and is NOT included here.
 #pragma once
 #include <cmath>
 #include <cstdarg>
@@ -16,6 +18,11 @@
 namespace nmfx {
 
 nmfx_status check_device(int device);
+// the device of a one-GPU call, checked: device_ids[0] when the caller names its one shard that way, else p->device
+inline nmfx_status single_gpu_device(const nmfx_problem *p) { return check_device(p->n_gpus == 1 && p->device_ids ? p->device_ids[0] : p->device); }
+
+// grid of an element-wise kernel that strides over `count` elements, 256 threads per workgroup
+inline unsigned grid1(long count) { const long b = (count + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b)); }
 
 // every entry point leaves the caller's current HIP device as it found it (torch and MATLAB hosts keep their own idea of "current")
 struct DeviceGuard {
@@ -219,6 +226,12 @@ inline size_t dsize(int dtype) { return dtype == NMFX_F64 ? 8 : 4; }
 // host (f32 / f64, pageable) <-> device fp32 through two pinned staging buffers, conversion on host threads (host_io.hip); upload: out = in / divide_by
 nmfx_status upload(hipStream_t st, const void *host, int dtype, float *dev, size_t count, double divide_by);
 nmfx_status download(hipStream_t st, const float *dev, int dtype, void *host, size_t count);
+// host array (f32 / f64) <-> device doubles: float64 as it is; fp32 through the pinned staging above and `tmp` (count floats), widened / rounded on the device
+nmfx_status ingest64(hipStream_t st, const void *host, int dtype, double *dev64, size_t count, DevBuf &tmp);
+nmfx_status egress64(hipStream_t st, const double *dev64, int dtype, void *host, size_t count, DevBuf &tmp);
+// host factor (f32 / f64) -> float64 master + its fp32 image; and back: a float64 host array gets the master, an fp32 one the image
+nmfx_status ingest_master(hipStream_t st, const void *host, int dtype, double *d64, float *d32, size_t count);
+nmfx_status egress_master(hipStream_t st, const double *d64, const float *d32, int dtype, void *host, size_t count);
 void host_minmax(const void *host, int dtype, size_t count, double *vmin, double *vmax);
 void staging_quiesce();   // the pinned staging buffers hold no reference to an event of a stream that is about to be handed back (host_io.hip)
 // per-thread account of the last blocking call (nmfx_last_call_timing)
@@ -245,6 +258,34 @@ inline bool mu_stop(int algorithm, const double *cost, int idx, double tolerance
     return cost[idx] < cost[idx - 1] && cost[idx - 1] - cost[idx] < tolerance;
 }
 nmfx_status validate_problem(const nmfx_problem *p, const nmfx_result *r, bool nmfsc, bool need_H_init = true);
+// per-source lambda / fixed flags (nmf.m:145-173 loops over the sources on one concatenated problem) as per-component vectors of length K >= K_total, the
+// lambdas as L (float for the fp32 engines, double for nmf64); components past K_total are the zero padding of the fused kernels: fixed, never updated.
+// The flags are stored as 0 / 1 (every device consumer tests them for non-zero only, and nmfx_engine_init normalises them itself)
+template <class L> struct SourceVectors {
+    std::vector<L> lw, lh;
+    std::vector<uint8_t> fw, fh;
+    bool all_wf = true, all_hf = true, any_lw = false, any_lh = false;   // over the K_total components of the problem
+};
+template <class L> SourceVectors<L> expand_sources(const nmfx_problem *p, int K) {
+    const int Kt = p->K_total;
+    SourceVectors<L> v;
+    v.lw.assign(K, L(0)); v.lh.assign(K, L(0)); v.fw.assign(K, 0); v.fh.assign(K, 0);
+    for (int k = Kt; k < K; ++k) v.fw[k] = v.fh[k] = 1;
+    for (int s = 0, k = 0; s < p->num_sources; ++s) {
+        const int Ks = p->K_s ? p->K_s[s] : Kt;
+        for (int q = 0; q < Ks; ++q, ++k) {
+            if (p->W_sparsity) v.lw[k] = (L)p->W_sparsity[s];
+            if (p->H_sparsity) v.lh[k] = (L)p->H_sparsity[s];
+            if (p->W_fixed) v.fw[k] = p->W_fixed[s] != 0;
+            if (p->H_fixed) v.fh[k] = p->H_fixed[s] != 0;
+            v.all_wf = v.all_wf && v.fw[k];
+            v.all_hf = v.all_hf && v.fh[k];
+            v.any_lw = v.any_lw || v.lw[k] != L(0);
+            v.any_lh = v.any_lh || v.lh[k] != L(0);
+        }
+    }
+    return v;
+}
 // Streams and events of the single-process multi-GPU drivers come out of a process-wide pool and go back to it, never destroyed: a MATLAB session calls
 // nmf() many times, and creating / destroying 8 streams + 32 events per call at a high call rate is what a rare host-heap corruption inside the runtime's
 // teardown went with (scripts/fuzz_campaign_r3.py multi_edge).  Callers drain a stream before they hand it back.

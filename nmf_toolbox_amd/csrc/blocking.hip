@@ -6,24 +6,6 @@ using namespace nmfx;
 
 namespace {
 
-// per-source lambda / fixed flags (nmf.m:145-173 loops over the sources on one concatenated problem) as per-component vectors of length K >= K_total;
-// components past K_total are the zero padding of the fused kernels: fixed, never updated
-void expand_sources(const nmfx_problem *p, int K, std::vector<float> &lw, std::vector<float> &lh, std::vector<uint8_t> &fw, std::vector<uint8_t> &fh) {
-    const int Kt = p->K_total;
-    lw.assign(K, 0.f); lh.assign(K, 0.f); fw.assign(K, 0); fh.assign(K, 0);
-    for (int k = Kt; k < K; ++k) fw[k] = fh[k] = 1;
-    for (int s = 0, k0 = 0; s < p->num_sources; ++s) {
-        const int Ks = p->K_s ? p->K_s[s] : Kt;
-        for (int k = k0; k < k0 + Ks; ++k) {
-            if (p->W_sparsity) lw[k] = (float)p->W_sparsity[s];
-            if (p->H_sparsity) lh[k] = (float)p->H_sparsity[s];
-            if (p->W_fixed) fw[k] = p->W_fixed[s];
-            if (p->H_fixed) fh[k] = p->H_fixed[s];
-        }
-        k0 += Ks;
-    }
-}
-
 // float64 host factors -> DEVICE doubles in the engine's (K-padded) layout, for nmfx_engine_init_f64: MATLAB's doubles reach the master copies unrounded.
 // W: m x Kt x T -> m x K x T (zero columns appended to every time slice); H: columns [col0, col0 + ncols) of the Kt x n array -> K x ncols (zero rows appended)
 nmfx_status stage_init64(hipStream_t st, const nmfx_problem *p, int K, long col0, long ncols, bool want_H, DevBuf &W0d, DevBuf &H0d) {
@@ -66,8 +48,7 @@ struct MultiDev {
     bool pad = false;
     int path = 0;                          // ... and the kernel path every shard is asked for
     long nz = 0;                           // constrainednmf: columns of Z
-    std::vector<float> lw, lh;             // expand_sources
-    std::vector<uint8_t> fw, fh;
+    SourceVectors<float> src;              // expand_sources
     size_t packed_count = 0;               // floats of the packed W-step sums: the same on every shard
     int ndev = 0;
     int dev[NMFX_MAX_GPUS];
@@ -139,7 +120,7 @@ nmfx_status MultiDev::alloc(int g) {
     d = nmfx_engine_desc{};
     d.m = m; d.n_local = nl; d.K_total = K; d.T = p->T; d.divergence = dv; d.alpha = p->alpha; d.beta = p->beta;
     d.halo_left = (int)hL[g]; d.halo_right = (int)hR[g]; d.n_valid = nl + hR[g];
-    d.lamW_col = lw.data(); d.lamH_row = lh.data(); d.fixW_col = fw.data(); d.fixH_row = fh.data();
+    d.lamW_col = src.lw.data(); d.lamH_row = src.lh.data(); d.fixW_col = src.fw.data(); d.fixH_row = src.fh.data();
     d.device = dev[g]; d.stream = st[g]; d.algorithm = algorithm; d.path = path; d.K_valid = pad ? Kt : 0; d.col_offset = lo[g];
     size_t pc = 0;
     TRY(nmfx_engine_packed_count(&d, &pc));
@@ -408,7 +389,7 @@ nmfx_status run_mu(const nmfx_problem *p, nmfx_result *r, int algorithm, bool sh
     const MuPlan plan = plan_mu(p, algorithm, sharded, shortest);
     const int K = M.K = plan.K;
     M.pad = plan.padded; M.path = plan.path;
-    expand_sources(p, K, M.lw, M.lh, M.fw, M.fh);
+    M.src = expand_sources<float>(p, K);
     const size_t mK = (size_t)p->m * K * p->T;
     for (int g = 0; g < N; ++g) TRY(M.alloc(g));
     TRY(M.alloc_workspaces());

@@ -13,6 +13,9 @@
 //                (R is the residual of the PREVIOUS iteration's state: its sum of squares is that iteration's cost, one pass late)
 //   W step       W_i .* (A_i*H_i') ./ max(W_all*(H_all*H_i'), eps), unit L2 columns   (numerator on the MFMA GEMM, denominator in Gram form)
 //   H step       H_i .* (W_i'*A_i) ./ max((W_i'*W_all_old)*H_all_old + lambda_i, eps)
+//
+// Shared with the other add-on drivers: grid1 and single_gpu_device (api_common.h).  Its own: the interleaving ingest of the complex arrays, the source
+// expansion (it also builds the row -> source maps and the phase switches) and its block reduction (see block_sum256 below).
 #include <chrono>
 
 #include "api_common.h"
@@ -154,6 +157,7 @@ __global__ __launch_bounds__(256) void cmf_epass(EParams p) {
     }
 }
 
+// (dev_reduce.h's reduction without its closing barrier -- this file's own, kept so that its kernels stay as they are; dev_reduce.h is not included here)
 __device__ inline double block_sum256(double x, double *sh) {   // deterministic: fixed shuffle tree, then the four waves in order
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
     __syncthreads();
@@ -238,8 +242,6 @@ __global__ __launch_bounds__(256) void cmf_cost(const double *parts, long np, co
     if (threadIdx.x == 0) *out = t + u;
 }
 
-unsigned grid1(long count) { long b = (count + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b)); }
-
 GemmParams gemm_params(long M, long N, long Kc, OpView A, OpView B, float *C, long ldc) {
     GemmParams g;
     memset(&g, 0, sizeof(g));
@@ -310,7 +312,7 @@ nmfx_status run_cmfwisa(const nmfx_problem *p, const void *V_imag, const void *P
     if (p->T != 1) { set_error("cmfwisa: T must be 1 (the convolutive variant is not implemented)"); return NMFX_ERR_UNSUPPORTED; }
     if (p->n_gpus > 1) { set_error("cmfwisa: one GPU only (n_gpus = %d)", p->n_gpus); return NMFX_ERR_UNSUPPORTED; }
     DeviceGuard dg_;
-    TRY(check_device(p->n_gpus == 1 && p->device_ids ? p->device_ids[0] : p->device));
+    TRY(single_gpu_device(p));
     const long m = p->m, n = p->n;
     const int K = p->K_total, I = p->num_sources;
     const size_t mn = (size_t)m * n;

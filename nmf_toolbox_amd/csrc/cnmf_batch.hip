@@ -1,6 +1,7 @@
 // cnmf (cnmf.m:155-258) on a BATCH of independent problems in one call: nmfx_cnmf_batch.  The problems share m, K, T and the configuration; problem b has its
 // own n_b columns, its own W_b (m x K x T), H_b, cost vector and stopping point.  The arithmetic and the launch structure are nmf_batch's (nmf_batch.hip,
-// DESIGN 4.10): V as fp32, everything else float64, every contraction on the fp64 matrix core, the pass kernel of nb_pass.h with its CONV operand.
+// DESIGN 4.10): V as fp32, everything else float64, every contraction on the fp64 matrix core, the pass kernel of nb_pass.h with its CONV operand; through
+// nb_pass.h also the shared block reduction (dev_reduce.h) and float64 staging (ingest64 / egress64, api_common.h).
 //
 // Device state: V fp32 m x N, the problems side by side; H K x N float64; of every W_b two copies written together, the master m x K x T x B
 // the update and the result use and the pass operand WC[b][i][kappa], kappa = (T-1-t)*K + k, rows of K*T contiguous doubles.  With that order
@@ -220,9 +221,9 @@ nmfx_status run_cnmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *
     NMFX_HIP(hipMemsetAsync(ddone.p, 0, (size_t)B * 4, st));
     NMFX_HIP(hipMemsetAsync(dcost.p, 0, (size_t)maxiter * B * 8, st));
     TRY(upload(st, p->V, p->dtype, Vd.as<float>(), mN, 1.0));
-    TRY(nb_ingest64(st, p->W_init, p->dtype, Wm.as<double>(), mKTB, tmp32));
+    TRY(ingest64(st, p->W_init, p->dtype, Wm.as<double>(), mKTB, tmp32));
     NMFX_HIP(hipStreamSynchronize(st));   // (the staging buffer is reused)
-    TRY(nb_ingest64(st, p->H_init, p->dtype, Hm.as<double>(), KN, tmp32));
+    TRY(ingest64(st, p->H_init, p->dtype, Hm.as<double>(), KN, tmp32));
     NMFX_HIP(hipStreamSynchronize(st));   // (the caller's pageable buffers and the host tables have been read)
     clock.end(&IoStats::ingest_s);
 
@@ -286,9 +287,9 @@ nmfx_status run_cnmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *
     for (int b = 0; b < B; ++b) { cost_len[b] = hdone[b]; longest = std::max(longest, hdone[b]); }
     r->cost_len = r->iters_run = longest;
     clock.end(&IoStats::iterate_s);
-    TRY(nb_egress64(st, Wm.as<double>(), p->dtype, r->W, mKTB, tmp32));
+    TRY(egress64(st, Wm.as<double>(), p->dtype, r->W, mKTB, tmp32));
     NMFX_HIP(hipStreamSynchronize(st));
-    TRY(nb_egress64(st, Hm.as<double>(), p->dtype, r->H, KN, tmp32));
+    TRY(egress64(st, Hm.as<double>(), p->dtype, r->H, KN, tmp32));
     NMFX_HIP(hipStreamSynchronize(st));
     clock.end(&IoStats::egress_s);
     return NMFX_OK;

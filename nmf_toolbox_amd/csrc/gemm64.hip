@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
-#include "nmfx_internal.h"
+#include "api_common.h"
 
 namespace nmfx {
 
@@ -237,7 +237,22 @@ nmfx_status launch_panel(hipStream_t st, const double *A, long lda, const float 
     return NMFX_OK;
 }
 
+// out = sum of `ns` slabs of `count` doubles, in slab order
+__global__ __launch_bounds__(256) void slab_sum64_kernel(const double *slabs, int ns, long count, double *out) {
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < count; e += (long)gridDim.x * 256) {
+        double t = 0.0;
+        for (int s = 0; s < ns; ++s) t += slabs[e + count * s];
+        out[e] = t;
+    }
+}
+
 }  // namespace
+
+nmfx_status slab_sum64(hipStream_t st, const double *slabs, int ns, long count, double *out) {
+    hipLaunchKernelGGL(slab_sum64_kernel, dim3(grid1(count)), dim3(256), 0, st, slabs, ns, count, out);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
 
 nmfx_status gemm64(hipStream_t st, long M, long N, long Kc, const double *A64, const float *A32, long lda, const double *B64, const float *B32, long ldb,
                    double *C64, float *C32, long ldc) {

@@ -244,6 +244,44 @@ nmfx_status download(hipStream_t st, const float *dev, int dtype, void *host, si
     return NMFX_OK;
 }
 
+// ---- float64 device state of the add-on drivers (nmf64, nmf_batch, cnmf_batch; wnmf's masters) ------------------------------------------------------
+// A float64 host array is copied as it is (8 bytes per element over PCIe, counted as such); an fp32 one goes through the pinned staging above.
+namespace {
+nmfx_status copy_in64(hipStream_t st, const void *host, double *dev64, size_t count) {
+    NMFX_HIP(hipMemcpyAsync(dev64, host, count * 8, hipMemcpyHostToDevice, st));
+    g_io.h2d_bytes_host += (double)count * 8.0;
+    g_io.h2d_bytes_pcie += (double)count * 8.0;
+    return NMFX_OK;
+}
+nmfx_status copy_out64(hipStream_t st, const double *dev64, void *host, size_t count) {
+    NMFX_HIP(hipMemcpyAsync(host, dev64, count * 8, hipMemcpyDeviceToHost, st));
+    g_io.d2h_bytes_host += (double)count * 8.0;
+    return NMFX_OK;
+}
+}  // namespace
+nmfx_status ingest64(hipStream_t st, const void *host, int dtype, double *dev64, size_t count, DevBuf &tmp) {
+    if (dtype == NMFX_F64) return copy_in64(st, host, dev64, count);
+    TRY(upload(st, host, dtype, tmp.as<float>(), count, 1.0));
+    return cvt_to_f64(st, tmp.as<float>(), dev64, (long)count);
+}
+nmfx_status egress64(hipStream_t st, const double *dev64, int dtype, void *host, size_t count, DevBuf &tmp) {
+    if (dtype == NMFX_F64) return copy_out64(st, dev64, host, count);
+    TRY(cvt_f64_to_f32(st, dev64, tmp.as<float>(), (long)count));
+    return download(st, tmp.as<float>(), dtype, host, count);
+}
+nmfx_status ingest_master(hipStream_t st, const void *host, int dtype, double *d64, float *d32, size_t count) {
+    if (dtype == NMFX_F64) {
+        TRY(copy_in64(st, host, d64, count));
+        return cvt_f64_to_f32(st, d64, d32, (long)count);
+    }
+    TRY(upload(st, host, dtype, d32, count, 1.0));
+    return cvt_to_f64(st, d32, d64, (long)count);
+}
+nmfx_status egress_master(hipStream_t st, const double *d64, const float *d32, int dtype, void *host, size_t count) {
+    if (dtype == NMFX_F64) return copy_out64(st, d64, host, count);
+    return download(st, d32, dtype, host, count);
+}
+
 // min / max of a host array (nmfsc.m:57-62: the sign check and the global rescale), on the same threads
 void host_minmax(const void *host, int dtype, size_t count, double *vmin, double *vmax) {
     const int T = io_threads();

@@ -1,7 +1,9 @@
 // The pass kernel, the decide kernel and the host helpers that nmf_batch.hip and cnmf_batch.hip share.  Included once by each of the two
-// translation units; everything lives in an anonymous namespace, so each gets its own instantiations.
+// translation units; everything lives in an anonymous namespace, so each gets its own instantiations.  The block reduction is dev_reduce.h's and the float64
+// staging (ingest64 / egress64) api_common.h's, as in the other add-on drivers; grid_of (a workgroup per item) is this pair's own.
 #pragma once
 #include "api_common.h"
+#include "dev_reduce.h"
 
 namespace nmfx {
 namespace {
@@ -24,16 +26,6 @@ struct NbProb {
     int hitem0;     // H step: one item per 64 columns
     int pad_;
 };
-
-__device__ inline double block_sum256(double x, double *sh) {   // deterministic: fixed shuffle tree, then the four waves in order
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
 
 struct NbPass {
     const NbProb *prob;
@@ -289,29 +281,7 @@ __global__ __launch_bounds__(256) void nb_decide(const NbDecide g) {
     }
 }
 
-unsigned grid_of(long count) { return (unsigned)(count < 1 ? 1 : (count > NB_MAX_GRID ? NB_MAX_GRID : count)); }
-
-// host array (p->dtype) -> device doubles: float64 as it is; fp32 through the pinned staging of host_io.hip into `tmp` and widened on the device
-nmfx_status nb_ingest64(hipStream_t st, const void *host, int dtype, double *dev, size_t count, DevBuf &tmp) {
-    if (dtype == NMFX_F64) {
-        NMFX_HIP(hipMemcpyAsync(dev, host, count * 8, hipMemcpyHostToDevice, st));
-        IoStats &io = io_stats();
-        io.h2d_bytes_host += (double)count * 8.0;
-        io.h2d_bytes_pcie += (double)count * 8.0;
-        return NMFX_OK;
-    }
-    TRY(upload(st, host, dtype, tmp.as<float>(), count, 1.0));
-    return cvt_to_f64(st, tmp.as<float>(), dev, (long)count);
-}
-nmfx_status nb_egress64(hipStream_t st, const double *dev, int dtype, void *host, size_t count, DevBuf &tmp) {
-    if (dtype == NMFX_F64) {
-        NMFX_HIP(hipMemcpyAsync(host, dev, count * 8, hipMemcpyDeviceToHost, st));
-        io_stats().d2h_bytes_host += (double)count * 8.0;
-        return NMFX_OK;
-    }
-    TRY(cvt_f64_to_f32(st, dev, tmp.as<float>(), (long)count));
-    return download(st, tmp.as<float>(), dtype, host, count);
-}
+unsigned grid_of(long count) { return (unsigned)(count < 1 ? 1 : (count > NB_MAX_GRID ? NB_MAX_GRID : count)); }   // one workgroup per item (grid1: per 256 elements)
 
 struct PooledStream {
     int dev;

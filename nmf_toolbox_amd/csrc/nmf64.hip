@@ -1,5 +1,7 @@
 // nmf (nmf.m:130-234) end to end in float64: nmfx_nmf_f64.  Every quantity is a double on the device and every m*n*K contraction runs on the fp64 matrix
-// core (v_mfma_f64_16x16x4_f64).  The fp32 paths (engine.hip, fused*.hip) are untouched; this file shares nothing with them but the host scaffolding.
+// core (v_mfma_f64_16x16x4_f64).  The fp32 paths (engine.hip, fused*.hip) are untouched.  Shared with the other add-on
+// drivers: the block reduction (dev_reduce.h), the slab sum (slab_sum64, gemm64.hip), and from api_common.h the float64 staging (ingest64 / egress64), the
+// source expansion (expand_sources), grid1 and single_gpu_device.
 //
 // Device state (column-major): V m x n, W m x K, H K x n, and the element maps A (and B) m x n of the divergence; V_hat = W*H itself never reaches memory.
 //     divergence              A                          B
@@ -33,6 +35,7 @@
 // 404 registers and scalar spills, one workgroup per CU, one V load at a time: 4.17 ms at the euclidean shape.  Kept: the 128 x 64 tile, V requested behind the
 // first stage, the map a template parameter and its loops rolled (see the epilogue): 1.91 ms.
 #include "api_common.h"
+#include "dev_reduce.h"
 
 namespace nmfx {
 namespace {
@@ -43,15 +46,6 @@ constexpr double EPS64 = 2.220446049250313e-16;   // MATLAB's eps, 2^-52
 constexpr int C64_BK = 16, C64_LDK = C64_BK + 2;
 enum Map64 { MAP_EUC = 0, MAP_KL = 1, MAP_IS = 2, MAP_AB = 3, MAP_ABD = 4 };
 
-__device__ inline double block_sum256(double x, double *sh) {   // deterministic: fixed shuffle tree, then the four waves in order
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
 // x.^p as the reference's array power evaluates it: the exponents with an exact form take it
 __device__ inline double pw(double x, double p) {
     if (p == 1.0) return x;
@@ -249,16 +243,6 @@ nmfx_status c64_launch(hipStream_t st, const C64Args &g, unsigned *grid_out = nu
 }
 long c64_map_grid(long m, long n) { return std::min<long>(((m + 127) / 128) * ((n + 63) / 64), C64_MAX_GRID); }   // (the 128 x 64 tiles of s_map)
 
-// out = sum of `ns` slabs of `count` doubles, in slab order
-__global__ __launch_bounds__(256) void n64_slab_sum(const double *slabs, int ns, long count, double *out) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < count; e += (long)gridDim.x * 256) {
-        double t = 0.0;
-        for (int s = 0; s < ns; ++s) t += slabs[e + count * s];
-        out[e] = t;
-    }
-}
-unsigned grid1(long count) { const long b = (count + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b)); }
-
 // a contraction whose output (M x N, ld M) is small next to its contracted extent: slabs of the contraction so that every CU gets work, summed in slab order
 struct Split64 {
     int ns = 1;
@@ -282,10 +266,7 @@ nmfx_status contract_nt(hipStream_t st, const double *X, long ldx, const double 
     if (N <= 32) TRY((c64_launch<4, 1, 2, 2, true, true, 0>(st, g)));
     else if (N <= 64) TRY((c64_launch<2, 2, 4, 2, true, true, 0>(st, g)));
     else TRY((c64_launch<2, 2, 4, 4, true, true, 0>(st, g)));
-    if (sp.ns > 1) {
-        hipLaunchKernelGGL(n64_slab_sum, dim3(grid1(M * N)), dim3(256), 0, st, slab, sp.ns, M * N, C);
-        NMFX_HIP(hipGetLastError());
-    }
+    if (sp.ns > 1) TRY(slab_sum64(st, slab, sp.ns, M * N, C));
     return NMFX_OK;
 }
 // C (M x N, ld M) = X' * Y with X L x M and Y L x N, both contiguous along the contraction (X[l + ldx*i], Y[l + ldy*j]): W'*A, W'*B, W'*W
@@ -296,10 +277,7 @@ nmfx_status contract_tn(hipStream_t st, const double *X, long ldx, const double 
     if (M <= 32) TRY((c64_launch<1, 4, 2, 2, false, false, 0>(st, g)));
     else if (M <= 64) TRY((c64_launch<2, 2, 2, 4, false, false, 0>(st, g)));
     else TRY((c64_launch<2, 2, 4, 4, false, false, 0>(st, g)));
-    if (sp.ns > 1) {
-        hipLaunchKernelGGL(n64_slab_sum, dim3(grid1(M * N)), dim3(256), 0, st, slab, sp.ns, M * N, C);
-        NMFX_HIP(hipGetLastError());
-    }
+    if (sp.ns > 1) TRY(slab_sum64(st, slab, sp.ns, M * N, C));
     return NMFX_OK;
 }
 
@@ -405,28 +383,6 @@ __global__ __launch_bounds__(256) void n64_cost_finish(const double *parts, long
     }
 }
 
-// host array (p->dtype) -> device doubles: float64 as it is; fp32 through the pinned staging of host_io.hip into `tmp` and widened on the device
-nmfx_status ingest64(hipStream_t st, const void *host, int dtype, double *dev, size_t count, DevBuf &tmp) {
-    if (dtype == NMFX_F64) {
-        NMFX_HIP(hipMemcpyAsync(dev, host, count * 8, hipMemcpyHostToDevice, st));
-        IoStats &io = io_stats();
-        io.h2d_bytes_host += (double)count * 8.0;
-        io.h2d_bytes_pcie += (double)count * 8.0;
-        return NMFX_OK;
-    }
-    TRY(upload(st, host, dtype, tmp.as<float>(), count, 1.0));
-    return cvt_to_f64(st, tmp.as<float>(), dev, (long)count);
-}
-nmfx_status egress64(hipStream_t st, const double *dev, int dtype, void *host, size_t count, DevBuf &tmp) {
-    if (dtype == NMFX_F64) {
-        NMFX_HIP(hipMemcpyAsync(host, dev, count * 8, hipMemcpyDeviceToHost, st));
-        io_stats().d2h_bytes_host += (double)count * 8.0;
-        return NMFX_OK;
-    }
-    TRY(cvt_f64_to_f32(st, dev, tmp.as<float>(), (long)count));
-    return download(st, tmp.as<float>(), dtype, host, count);
-}
-
 // ---- the driver ----------------------------------------------------------------------------------------------------------------------------------------
 nmfx_status run_nmf_f64(const nmfx_problem *p, nmfx_result *r) {
     TRY(validate_problem(p, r, false, true));
@@ -441,28 +397,14 @@ nmfx_status run_nmf_f64(const nmfx_problem *p, nmfx_result *r) {
         default: set_error("nmf_f64: divergence %d has no update equations (nmf.m:165-166)", p->divergence); return NMFX_ERR_INVALID;
     }
     DeviceGuard dg_;
-    TRY(check_device(p->n_gpus == 1 && p->device_ids ? p->device_ids[0] : p->device));
+    TRY(single_gpu_device(p));
     const long m = p->m, n = p->n;
-    const int K = p->K_total, S = p->num_sources;
+    const int K = p->K_total;
     const size_t mn = (size_t)m * n, mK = (size_t)m * K, Kn = (size_t)K * n, KK = (size_t)K * K;
     const double alpha = p->alpha, beta = p->beta;
     const double expo = map == MAP_AB ? 1.0 / alpha : (map == MAP_ABD ? 1.0 / beta : 1.0);
-    // per-component lambda and switches (the source's value repeated)
-    std::vector<double> lw(K, 0.0), lh(K, 0.0);
-    std::vector<uint8_t> fw(K, 0), fh(K, 0);
-    bool all_wf = true, all_hf = true, any_lam = false;
-    for (int s = 0, k = 0; s < S; ++s) {
-        const int ks = p->K_s ? p->K_s[s] : K;
-        for (int q = 0; q < ks; ++q, ++k) {
-            lw[k] = p->W_sparsity ? p->W_sparsity[s] : 0.0;
-            lh[k] = p->H_sparsity ? p->H_sparsity[s] : 0.0;
-            fw[k] = p->W_fixed ? (p->W_fixed[s] != 0) : 0;
-            fh[k] = p->H_fixed ? (p->H_fixed[s] != 0) : 0;
-            all_wf = all_wf && fw[k];
-            all_hf = all_hf && fh[k];
-            any_lam = any_lam || lw[k] != 0.0 || lh[k] != 0.0;
-        }
-    }
+    const SourceVectors<double> src = expand_sources<double>(p, K);   // per-component lambda and switches (the source's value repeated)
+    const bool all_wf = src.all_wf, all_hf = src.all_hf, any_lam = src.any_lw || src.any_lh;
     const bool has_a = map != MAP_EUC, has_b = map == MAP_IS || map == MAP_AB || map == MAP_ABD;
     const Split64 spW(true, m, K, n), spH(false, K, n, m), spG(true, K, K, n), spC(false, K, K, m);
     const size_t slab_doubles = std::max(std::max(spW.scratch_doubles(m, K), spH.scratch_doubles(K, n)), std::max(spG.scratch_doubles(K, K), spC.scratch_doubles(K, K)));
@@ -483,10 +425,10 @@ nmfx_status run_nmf_f64(const nmfx_problem *p, nmfx_result *r) {
     hipStream_t st = nullptr;
     StreamDrain drain_(st);
     CallClock clock;
-    NMFX_HIP(hipMemcpyAsync(lamW, lw.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(lamH, lh.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(fixW, fw.data(), (size_t)K, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(fixH, fh.data(), (size_t)K, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(lamW, src.lw.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(lamH, src.lh.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(fixW, src.fw.data(), (size_t)K, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(fixH, src.fh.data(), (size_t)K, hipMemcpyHostToDevice, st));
     NMFX_HIP(hipMemsetAsync(l1, 0, (size_t)K * 8, st));
     TRY(ingest64(st, p->V, p->dtype, V, mn, tmp32));
     TRY(ingest64(st, p->W_init, p->dtype, W, mK, tmp32));

@@ -1,6 +1,6 @@
 // nmf (nmf.m:130-234) on a BATCH of independent problems in one call: nmfx_nmf_batch.  The problems share m, K and the configuration; problem b has its
-// own n_b columns, its own W_b, H_b, cost vector and stopping point.  Nothing here is shared with the one-problem paths (engine.hip, fused*.hip, nmf64.hip)
-// but the host scaffolding.
+// own n_b columns, its own W_b, H_b, cost vector and stopping point.  The one-problem paths (engine.hip, fused*.hip, nmf64.hip) are untouched; shared
+// with the other add-on drivers are the block reduction (dev_reduce.h) and the float64 staging (ingest64 / egress64, api_common.h), both through nb_pass.h.
 //
 // Device state: V as fp32, m x N column-major, the problems side by side along the columns (N = sum n_b); H (K x N) and every W_b as float64.
 // Both factors are contracted as rows of K contiguous doubles: H is that already (H[k + K*j]); of W there are two copies, the column-major one the W update and
@@ -183,9 +183,9 @@ nmfx_status run_nmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *o
     NMFX_HIP(hipMemsetAsync(ddone.p, 0, (size_t)B * 4, st));
     NMFX_HIP(hipMemsetAsync(dcost.p, 0, (size_t)maxiter * B * 8, st));
     TRY(upload(st, p->V, p->dtype, Vd.as<float>(), mN, 1.0));
-    TRY(nb_ingest64(st, p->W_init, p->dtype, Wm.as<double>(), mKB, tmp32));
+    TRY(ingest64(st, p->W_init, p->dtype, Wm.as<double>(), mKB, tmp32));
     NMFX_HIP(hipStreamSynchronize(st));   // (the staging buffer is reused)
-    TRY(nb_ingest64(st, p->H_init, p->dtype, Hm.as<double>(), KN, tmp32));
+    TRY(ingest64(st, p->H_init, p->dtype, Hm.as<double>(), KN, tmp32));
     NMFX_HIP(hipStreamSynchronize(st));   // (the caller's pageable buffers and the host tables have been read)
     clock.end(&IoStats::ingest_s);
 
@@ -242,9 +242,9 @@ nmfx_status run_nmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *o
     for (int b = 0; b < B; ++b) { cost_len[b] = hdone[b]; longest = std::max(longest, hdone[b]); }
     r->cost_len = r->iters_run = longest;
     clock.end(&IoStats::iterate_s);
-    TRY(nb_egress64(st, Wm.as<double>(), p->dtype, r->W, mKB, tmp32));
+    TRY(egress64(st, Wm.as<double>(), p->dtype, r->W, mKB, tmp32));
     NMFX_HIP(hipStreamSynchronize(st));
-    TRY(nb_egress64(st, Hm.as<double>(), p->dtype, r->H, KN, tmp32));
+    TRY(egress64(st, Hm.as<double>(), p->dtype, r->H, KN, tmp32));
     NMFX_HIP(hipStreamSynchronize(st));
     clock.end(&IoStats::egress_s);
     return NMFX_OK;

@@ -249,6 +249,9 @@ nmfx_status w_normalize(hipStream_t st, float *W, long m, int K, int T, const do
 // C (M x N) = A * B accumulated in float64 on the fp64 matrix core (gemm64.hip); A(i, k) = A[i + lda*k], B(k, j) = B[k + ldb*j], each fp32 or float64
 nmfx_status gemm64(hipStream_t st, long M, long N, long Kc, const double *A64, const float *A32, long lda, const double *B64, const float *B32, long ldb,
                    double *C64, float *C32, long ldc);
+// out = the sum of `ns` slabs of `count` doubles (slab s at slabs + s*count), added in slab order: what closes a float64 contraction that was split into
+// slabs (nmf64's contract_nt / contract_tn, seminmf's Gram64) -- no atomics, run to run identical (gemm64.hip)
+nmfx_status slab_sum64(hipStream_t st, const double *slabs, int ns, long count, double *out);
 constexpr int NMFX_MAX_GPUS = 16;
 struct PeerPtrs { float *p[NMFX_MAX_GPUS]; };
 nmfx_status peer_reduce(hipStream_t st, const PeerPtrs &bufs, int ndev, int self, long off, long count);

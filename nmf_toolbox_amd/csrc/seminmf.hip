@@ -11,9 +11,13 @@
 //            L = chol(G), Ginv = L^-T*L^-1, W = N*Ginv
 //   H step   B = W'*V on v_mfma_f32_32x32x2_f32, C = W'*W, H .* sqrt((B+ + C-*H) ./ (B- + C+*H)) -- fused: B and the C*H products stay on chip
 //   cost     0.5*||V||^2 - <B, H> + 0.5*<C, H*H'> (Gram form; below 5 % of 0.5*||V||^2 an explicit float64 residual pass, sticky)
+//
+// Shared with the other add-on drivers: the block reduction (dev_reduce.h), the slab sum behind Gram64 (slab_sum64, gemm64.hip), grid1 and single_gpu_device
+// (api_common.h).  The ingest and egress of W and H stay open-coded: their order on the stream (both copies, then both conversions) is not ingest_master's.
 #include <chrono>
 
 #include "api_common.h"
+#include "dev_reduce.h"
 
 namespace nmfx {
 namespace {
@@ -22,18 +26,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int SN_FUSED_MAX_K = 256;
 constexpr double SN_EXACT_FRACTION = 0.05;   // below this share of 0.5*||V||^2 the Gram form no longer resolves the cost: explicit residual pass
-
-unsigned grid1(long count) { long b = (count + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b)); }
-
-__device__ inline double block_sum256(double x, double *sh) {   // deterministic: fixed shuffle tree, then the four waves in order
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
 
 // ---- small float64 helpers ------------------------------------------------------------------------------------------------------------------
 // out (cols x rows, leading dimension ldo) = in' (rows x cols), float64 and / or an fp32 image (either may be NULL); T = double or float.  A grid-stride loop
@@ -63,14 +55,6 @@ nmfx_status transpose64(hipStream_t st, const T *in, long rows, long cols, doubl
     hipLaunchKernelGGL((sn_transpose<T>), dim3((unsigned)std::min<long>(tiles, 65536)), dim3(256), 0, st, in, rows, cols, ldo ? ldo : cols, out, out32);
     NMFX_HIP(hipGetLastError());
     return NMFX_OK;
-}
-// out = sum of `ns` slabs of `count` doubles, in slab order
-__global__ __launch_bounds__(256) void sn_slab_sum(const double *slabs, int ns, long count, double *out) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < count; e += (long)gridDim.x * 256) {
-        double t = 0.0;
-        for (int s = 0; s < ns; ++s) t += slabs[e + count * s];
-        out[e] = t;
-    }
 }
 // sum of squares of an fp32 array, one partial per workgroup
 __global__ __launch_bounds__(256) void sn_sumsq(const float *x, long count, double *partials) {
@@ -116,9 +100,7 @@ struct Gram64 {
             const long l0 = (long)s * chunk, len = std::min(chunk, L - l0);
             TRY(gemm64(st, K, K, len, X + (size_t)K * l0, nullptr, K, Xt + l0, nullptr, L, slab + (size_t)s * K * K, nullptr, K));
         }
-        hipLaunchKernelGGL(sn_slab_sum, dim3(grid1((long)K * K)), dim3(256), 0, st, slab, ns, (long)K * K, G);
-        NMFX_HIP(hipGetLastError());
-        return NMFX_OK;
+        return slab_sum64(st, slab, ns, (long)K * K, G);
     }
 };
 
@@ -671,7 +653,7 @@ nmfx_status run_seminmf(const nmfx_problem *p, nmfx_result *r) {
     const int K = p->K_total;
     if (K > n) { set_error("seminmf: num_basis_elems = %d > size(V, 2) = %ld: H*H' is singular", K, n); return NMFX_ERR_INVALID; }
     DeviceGuard dg_;
-    TRY(check_device(p->n_gpus == 1 && p->device_ids ? p->device_ids[0] : p->device));
+    TRY(single_gpu_device(p));
     const bool wf = p->W_fixed && p->W_fixed[0], hf = p->H_fixed && p->H_fixed[0];
     const bool fits = K <= SN_FUSED_MAX_K && m >= 64 && n >= 64;
     if (p->path == 2 && !fits) { set_error("seminmf: nmfx_path = 2 needs the fused H pass (K <= %d, m and n >= 64)", SN_FUSED_MAX_K); return NMFX_ERR_UNSUPPORTED; }

@@ -29,7 +29,10 @@
 // Second products A*H', B*H', W'*A, W'*B: the library's pipelined fp32 GEMM (gemm_auto, slabs over the long contraction when the output is small).
 // Schedule (nmf64's): the cost of iteration t is the by-product of the first map pass of iteration t + 1, plus one cost-only pass after the last iteration;
 // with the stop rule on, the host reads those 8 bytes BEFORE the W update of t + 1 is launched, so a stop returns W(t), H(t) without a spare copy.
+// Shared with the other add-on drivers: the block reduction (dev_reduce.h), and from api_common.h the staging of the float64 masters (ingest_master /
+// egress_master), the source expansion (expand_sources), grid1 and single_gpu_device.
 #include "api_common.h"
+#include "dev_reduce.h"
 #include "gemm_common.h"
 
 namespace nmfx {
@@ -48,16 +51,6 @@ struct WMapArgs {
     int K;
     double *partials;       // [gridDim.x] weighted data-fit partials of a cost pass
 };
-
-__device__ inline double wblock_sum256(double x, double *sh) {   // deterministic: fixed shuffle tree, then the four waves in order
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
 
 template <int MAP, bool STORE, bool COST>
 __global__ __launch_bounds__(256, 2) void wmap_kernel(const WMapArgs g) {
@@ -166,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void wmap_kernel(const WMapArgs g) {
         }
     }
     if constexpr (COST) {
-        part = wblock_sum256(part, sh);
+        part = block_sum256(part, sh);
         if (tid == 0) g.partials[blockIdx.x] = part;
     }
 }
@@ -193,28 +186,6 @@ __global__ __launch_bounds__(256) void wnmf_prepare(float *V, const float *M, fl
         if (MV) MV[e] = on ? w * v : 0.0f;
     }
 }
-unsigned grid1(long count) { const long b = (count + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b)); }
-
-// host factor (p->dtype) -> float64 master + fp32 image
-nmfx_status ingest_factor(hipStream_t st, const void *host, int dtype, double *d64, float *d32, size_t count) {
-    if (dtype == NMFX_F64) {
-        NMFX_HIP(hipMemcpyAsync(d64, host, count * 8, hipMemcpyHostToDevice, st));
-        IoStats &io = io_stats();
-        io.h2d_bytes_host += (double)count * 8.0;
-        io.h2d_bytes_pcie += (double)count * 8.0;
-        return cvt_f64_to_f32(st, d64, d32, (long)count);
-    }
-    TRY(upload(st, host, dtype, d32, count, 1.0));
-    return cvt_to_f64(st, d32, d64, (long)count);
-}
-nmfx_status egress_factor(hipStream_t st, const double *d64, const float *d32, int dtype, void *host, size_t count) {
-    if (dtype == NMFX_F64) {
-        NMFX_HIP(hipMemcpyAsync(host, d64, count * 8, hipMemcpyDeviceToHost, st));
-        io_stats().d2h_bytes_host += (double)count * 8.0;
-        return NMFX_OK;
-    }
-    return download(st, d32, dtype, host, count);
-}
 
 nmfx_status run_wnmf(const nmfx_problem *p, const void *Mhost, nmfx_result *r) {
     TRY(validate_problem(p, r, false, true));
@@ -230,26 +201,12 @@ nmfx_status run_wnmf(const nmfx_problem *p, const void *Mhost, nmfx_result *r) {
         default: set_error("wnmf: divergence %d has no update equations (nmf.m:165-166)", p->divergence); return NMFX_ERR_INVALID;
     }
     DeviceGuard dg_;
-    TRY(check_device(p->n_gpus == 1 && p->device_ids ? p->device_ids[0] : p->device));
+    TRY(single_gpu_device(p));
     const long m = p->m, n = p->n;
-    const int K = p->K_total, S = p->num_sources;
+    const int K = p->K_total;
     const size_t mn = (size_t)m * n, mK = (size_t)m * K, Kn = (size_t)K * n;
-    std::vector<float> lw(K, 0.0f), lh(K, 0.0f);
-    std::vector<uint8_t> fw(K, 0), fh(K, 0);
-    bool all_wf = true, all_hf = true, any_lw = false, any_lh = false;
-    for (int s = 0, k = 0; s < S; ++s) {
-        const int ks = p->K_s ? p->K_s[s] : K;
-        for (int q = 0; q < ks; ++q, ++k) {
-            lw[k] = (float)(p->W_sparsity ? p->W_sparsity[s] : 0.0);
-            lh[k] = (float)(p->H_sparsity ? p->H_sparsity[s] : 0.0);
-            fw[k] = p->W_fixed ? (p->W_fixed[s] != 0) : 0;
-            fh[k] = p->H_fixed ? (p->H_fixed[s] != 0) : 0;
-            all_wf = all_wf && fw[k];
-            all_hf = all_hf && fh[k];
-            any_lw = any_lw || lw[k] != 0.0f;
-            any_lh = any_lh || lh[k] != 0.0f;
-        }
-    }
+    const SourceVectors<float> src = expand_sources<float>(p, K);
+    const bool all_wf = src.all_wf, all_hf = src.all_hf, any_lw = src.any_lw, any_lh = src.any_lh;
     const bool own_b = map != WM_KL;   // euclidean: A = M.*V (constant), B per pass; kl: A per pass, B = M itself; is: both per pass
     const size_t gscratch = std::max(gemm_scratch_bytes(m, K, n), gemm_scratch_bytes(K, n, m));
     const long np = wmap_grid(m, n);
@@ -271,14 +228,14 @@ nmfx_status run_wnmf(const nmfx_problem *p, const void *Mhost, nmfx_result *r) {
     hipStream_t st = nullptr;
     StreamDrain drain_(st);
     CallClock clock;
-    NMFX_HIP(hipMemcpyAsync(lamW, lw.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(lamH, lh.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(fixW, fw.data(), (size_t)K, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(fixH, fh.data(), (size_t)K, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(lamW, src.lw.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(lamH, src.lh.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(fixW, src.fw.data(), (size_t)K, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(fixH, src.fh.data(), (size_t)K, hipMemcpyHostToDevice, st));
     TRY(upload(st, p->V, p->dtype, V, mn, 1.0));
     TRY(upload(st, Mhost, p->dtype, M, mn, 1.0));
-    TRY(ingest_factor(st, p->W_init, p->dtype, W64, W, mK));
-    TRY(ingest_factor(st, p->H_init, p->dtype, H64, H, Kn));
+    TRY(ingest_master(st, p->W_init, p->dtype, W64, W, mK));
+    TRY(ingest_master(st, p->H_init, p->dtype, H64, H, Kn));
     hipLaunchKernelGGL(wnmf_prepare, dim3(grid1((long)mn)), dim3(256), 0, st, V, M, map == WM_EUC ? A : nullptr, (long)mn);
     NMFX_HIP(hipGetLastError());
     NMFX_HIP(hipStreamSynchronize(st));   // (the caller's pageable buffers and the host vectors above have been read)
@@ -357,9 +314,9 @@ nmfx_status run_wnmf(const nmfx_problem *p, const void *Mhost, nmfx_result *r) {
     NMFX_HIP(hipMemcpy(r->cost, dcost.p, (size_t)it * 8, hipMemcpyDeviceToHost));
     r->cost_len = r->iters_run = it;
     clock.end(&IoStats::iterate_s);
-    TRY(egress_factor(st, W64, W, p->dtype, r->W, mK));
+    TRY(egress_master(st, W64, W, p->dtype, r->W, mK));
     NMFX_HIP(hipStreamSynchronize(st));
-    TRY(egress_factor(st, H64, H, p->dtype, r->H, Kn));
+    TRY(egress_master(st, H64, H, p->dtype, r->H, Kn));
     NMFX_HIP(hipStreamSynchronize(st));
     clock.end(&IoStats::egress_s);
     return NMFX_OK;
