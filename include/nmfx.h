@@ -210,6 +210,17 @@ nmfx_status nmfx_nmf_f64(const nmfx_problem *p, nmfx_result *r);
  * NMFX_ERR_NOMEM with the byte count in the message: the call holds 4*m*n*(3 kl | 4 euclidean, is) bytes (V, M and the mapped operands as fp32) plus
  * O((m + n)*K).  nmfx_last_call_timing describes it. */
 nmfx_status nmfx_wnmf(const nmfx_problem *p, const void *M, nmfx_result *r);
+/* [W,H,cost] = weighted convolutive nmf: cnmf.m:1 (hot loop cnmf.m:155-258) with every element of the data fit weighted by M (m x n, p->dtype,
+ * column-major, >= 0).  With S = sum_t W_t * rshift_t(H) the mapped operands A, B and the cost are nmfx_wnmf's; the W step contracts N_t = A*rshift_t(H)',
+ * P_t = B*rshift_t(H)' per t (diag terms as column sums per (k, t)) and normalises W(:,k,:) to Frobenius norm T; the H step contracts
+ * sum_t W_t'*lshift_t(A) and sum_t W_t'*lshift_t(B), where the columns the shift reads past the end are 0 -- except B for kl, where they are 1: with
+ * M == 1 everywhere that is cnmf.m:220-221 (V_pos is not shifted for kl), and the call computes what nmfx_cnmf computes.  Where M == 0 an element
+ * contributes exactly 0 and V is never looked at there.  W_init (m x K_total x T) is normalised and H_init rescaled for every source (cnmf.m:157-166).  A
+ * new entry point; no structure grows, so NMFX_VERSION stays 600.  Fields as for nmfx_wnmf with T = the context length: path is ignored, NMFX_DIV_AB,
+ * T > 64, n_gpus > 1 and multi_backend != 0 are NMFX_ERR_UNSUPPORTED, a NULL M or n < T - 1 is NMFX_ERR_INVALID.  The call holds
+ * 4*m*n*(3 kl | 4 euclidean, is) + K_total*T*(20*m + 8*n) bytes (no more than 16*K_total*T*(m + n) while m <= 2*n) plus O((m + n)*K_total); a failed
+ * allocation is NMFX_ERR_NOMEM.  nmfx_last_call_timing describes it. */
+nmfx_status nmfx_wcnmf(const nmfx_problem *p, const void *M, nmfx_result *r);
 /* `batch` independent nmf problems (nmf.m:1, hot loop nmf.m:143-225) in one call: they share m, K_total and the configuration, problem b has its own
  * n_b = col_offsets[b + 1] - col_offsets[b] >= 1 columns, its own W_b, H_b, cost vector and stopping point.  Result b is what nmfx_nmf returns for problem b
  * alone; a problem whose stop rule fires at iteration t keeps W(t), H(t) and a cost vector of length t while the others run on.  A new entry point; no

@@ -14,6 +14,7 @@
     W, H, cost = nmf_batch(Vs, num_basis_elems, config)           nmf.m:1 per problem (lists: B independent problems in one call)
     W, H, cost = cnmf_batch(Vs, num_basis_elems, context_len, config)   cnmf.m:1 per problem (lists: B independent problems in one call)
     W, H, cost = wnmf(V, M, num_basis_elems, config)              nmf.m:1 with per-entry weights M >= 0 (missing or unreliable data)
+    W, H, cost = wcnmf(V, M, num_basis_elems, context_len, config)   cnmf.m:1 with per-entry weights M >= 0
 
 Same argument meaning, defaults and error behaviour as the MATLAB functions (a MATLAB cell array is
 a Python list, a struct a dict; errors are ValueError carrying the reference's message).  This file
@@ -257,6 +258,40 @@ def nmf(V, num_basis_elems, config=None, device=0):
 _DIV_WNMF = {"euclidean": _lib.DIV_EUCLIDEAN, "kl_divergence": _lib.DIV_KL, "kl": _lib.DIV_KL, "is_divergence": _lib.DIV_IS, "is": _lib.DIV_IS}
 
 
+def _weighted_inputs(fn, V, M, config):
+    """What wnmf and wcnmf check before anything else, with `fn` in every message: the refused extensions, the divergence, V a matrix, M of V's shape and
+    of a real kind with finite weights >= 0.  Returns V and M as they travel (M in V's dtype, column-major) and the divergence's name."""
+    cfg0 = config if config else {}
+    try:
+        _precision(cfg0, fn)     # (raises for 'float64' / 'double' -- nothing runs silently in another precision -- and for invalid values)
+    except ValueError as e:
+        raise ValueError(str(e) if fn in str(e) else fn + ": " + str(e)) from None
+    if cfg0.get("nmfx_gpus", None) is not None or cfg0.get("nmfx_multi_backend", None) is not None:
+        raise ValueError("%s runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported" % fn)
+    div = cfg0.get("divergence", "euclidean")
+    if div in ("ab_divergence", "ab"):
+        raise ValueError("%s has no alpha-beta divergence: its divergences are 'euclidean', 'kl' ('kl_divergence') and 'is' ('is_divergence')" % fn)
+    if not isinstance(div, str) or div not in _DIV_WNMF:
+        raise ValueError("%s: no update equations defined for cost function with divergence type %s" % (fn, div))
+    V = _as_data(V)
+    if V.ndim != 2:
+        raise ValueError("%s: V must be a matrix" % fn)
+    M = np.asarray(M)
+    if M.shape != V.shape:
+        raise ValueError("%s: M must have the shape of V, %r; got %r" % (fn, V.shape, M.shape))
+    if M.dtype.kind not in "buif":
+        raise ValueError("%s: M must be bool, integer or float; got %s" % (fn, M.dtype))
+    if M.dtype.kind == "f" and not np.all(np.isfinite(M)):
+        raise ValueError("%s: every weight in M must be finite" % fn)
+    if M.dtype.kind in "if" and M.size and M.min() < 0:
+        raise ValueError("%s: every weight in M must be >= 0" % fn)
+    with np.errstate(over="ignore"):     # (a float64 weight beyond float32's range becomes Inf and is refused below)
+        Mf = _f_order(M, V.dtype)
+    if not np.all(np.isfinite(Mf)):
+        raise ValueError("%s: every weight in M must be finite in V's dtype (%s)" % (fn, V.dtype))
+    return V, Mf, div
+
+
 def wnmf(V, M, num_basis_elems, config=None, device=0):
     """W, H, cost = wnmf(V, M, num_basis_elems, config): weighted NMF -- nmf (nmf.m:1) with every element of the data fit weighted by M >= 0, for
     missing or unreliable entries of V.  With S = W*H:
@@ -275,39 +310,50 @@ def wnmf(V, M, num_basis_elems, config=None, device=0):
     factors, maxiter, tolerance, seed: the defaults and the arrays drawn are nmf's), with divergence 'euclidean', 'kl' / 'kl_divergence' or
     'is' / 'is_divergence'.  One GPU and fp32 device arithmetic with float64 master copies of W and H: nmfx_gpus, nmfx_multi_backend and
     nmfx_precision='float64' are refused, nmfx_path is ignored (there is one path)."""
-    cfg0 = config if config else {}
-    try:
-        _precision(cfg0, "wnmf")     # (raises for 'float64' / 'double' -- nothing runs silently in another precision -- and for invalid values)
-    except ValueError as e:
-        raise ValueError(str(e) if "wnmf" in str(e) else "wnmf: " + str(e)) from None
-    if cfg0.get("nmfx_gpus", None) is not None or cfg0.get("nmfx_multi_backend", None) is not None:
-        raise ValueError("wnmf runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported")
-    div = cfg0.get("divergence", "euclidean")
-    if div in ("ab_divergence", "ab"):
-        raise ValueError("wnmf has no alpha-beta divergence: its divergences are 'euclidean', 'kl' ('kl_divergence') and 'is' ('is_divergence')")
-    if not isinstance(div, str) or div not in _DIV_WNMF:
-        raise ValueError("wnmf: no update equations defined for cost function with divergence type " + str(div))
-    V = _as_data(V)
-    if V.ndim != 2:
-        raise ValueError("wnmf: V must be a matrix")
-    M = np.asarray(M)
-    if M.shape != V.shape:
-        raise ValueError("wnmf: M must have the shape of V, %r; got %r" % (V.shape, M.shape))
-    if M.dtype.kind not in "buif":
-        raise ValueError("wnmf: M must be bool, integer or float; got %s" % M.dtype)
-    if M.dtype.kind == "f" and not np.all(np.isfinite(M)):
-        raise ValueError("wnmf: every weight in M must be finite")
-    if M.dtype.kind in "if" and M.size and M.min() < 0:
-        raise ValueError("wnmf: every weight in M must be >= 0")
-    with np.errstate(over="ignore"):     # (a float64 weight beyond float32's range becomes Inf and is refused below)
-        Mf = _f_order(M, V.dtype)
-    if not np.all(np.isfinite(Mf)):
-        raise ValueError("wnmf: every weight in M must be finite in V's dtype (%s)" % V.dtype)
+    V, Mf, div = _weighted_inputs("wnmf", V, M, config)
     Ks = [int(k) for k in (num_basis_elems if _is_cell(num_basis_elems) else [num_basis_elems])]   # nmf.m:114-117
     cfg, W, H, is_W_cell, is_H_cell = _validate(V, Ks, 1, config, False)                           # nmf.m:118
     lib = _lib.load()
     Wl, Hl, cost = _run_mu(lib.nmfx_wnmf, V, Ks, 1, cfg, W, H, _DIV_WNMF[div], device, extra=(_fptr(Mf),))
     Wl = [w[:, :, 0] for w in Wl]
+    return (Wl if is_W_cell else Wl[0]), (Hl if is_H_cell else Hl[0]), cost
+
+
+WCNMF_MAX_CONTEXT = 64
+
+
+def wcnmf(V, M, num_basis_elems, context_len, config=None, device=0):
+    """W, H, cost = wcnmf(V, M, num_basis_elems, context_len, config): weighted convolutive NMF -- cnmf (cnmf.m:1) with every element of the data fit
+    weighted by M >= 0, for missing or unreliable entries of V.  With T = context_len, S = sum_t W(:,:,t) * rshift_t(H) and wnmf's table of A, B and d(V, S):
+
+        W step   per t: N_t = A*rshift_t(H)', P_t = B*rshift_t(H)' in cnmf.m:187-194, then W(:,k,:) scaled to Frobenius norm T (cnmf.m:196-199)
+        H step   Gn = sum_t W_t'*lshift_t(A), Gp = sum_t W_t'*lshift_t(Bext), H <- H.*(Gn ./ max(Gp + lambda_H, eps)); the columns a shift reads past
+                 the end are 0, except that Bext is 1 there for 'kl' (cnmf.m:220-221 does not shift V_pos for kl: with M == 1 this is its denominator)
+        cost     sum(M.*d(V, S)) + the sparsity terms; the stop rule is cnmf's
+
+    Where M == 0 the entry contributes exactly nothing and V is never looked at there: it may be NaN, Inf or negative.  With M == 1 everywhere the result
+    is cnmf's.  W is m-by-K-by-T (m-by-K when T == 1); lists come back for several sources, as from cnmf.
+
+    M is wnmf's: the shape of V; bool, integer or float; it travels in V's dtype; a negative or non-finite weight is a ValueError.  num_basis_elems,
+    context_len and config are cnmf's (W_init, H_init, sparsities, fixed factors, maxiter, tolerance, seed / rng: the defaults and the arrays drawn are
+    cnmf's), with divergence 'euclidean', 'kl' / 'kl_divergence' or 'is' / 'is_divergence'.  1 <= context_len <= 64 and n >= context_len - 1.  One GPU and
+    fp32 device arithmetic with float64 master copies of W and H: nmfx_gpus, nmfx_multi_backend and nmfx_precision='float64' are refused, nmfx_path is
+    ignored (there is one path)."""
+    V, Mf, div = _weighted_inputs("wcnmf", V, M, config)
+    try:
+        T = int(context_len)
+    except (TypeError, ValueError):
+        raise ValueError("wcnmf: context_len must be an integer from 1 to %d; got %r" % (WCNMF_MAX_CONTEXT, context_len)) from None
+    if T != context_len or T < 1 or T > WCNMF_MAX_CONTEXT:
+        raise ValueError("wcnmf: context_len must be an integer from 1 to %d; got %r" % (WCNMF_MAX_CONTEXT, context_len))
+    if V.shape[1] < T - 1:
+        raise ValueError("wcnmf: V has %d columns, fewer than context_len - 1 = %d" % (V.shape[1], T - 1))
+    Ks = [int(k) for k in (num_basis_elems if _is_cell(num_basis_elems) else [num_basis_elems])]
+    cfg, W, H, is_W_cell, is_H_cell = _validate(V, Ks, T, config, True)                            # cnmf.m:131
+    lib = _lib.load()
+    Wl, Hl, cost = _run_mu(lib.nmfx_wcnmf, V, Ks, T, cfg, W, H, _DIV_WNMF[div], device, extra=(_fptr(Mf),))
+    if T == 1:                                             # rand(m,K,1) is a matrix in MATLAB
+        Wl = [w[:, :, 0] for w in Wl]
     return (Wl if is_W_cell else Wl[0]), (Hl if is_H_cell else Hl[0]), cost
 
 
