@@ -1,0 +1,99 @@
+"""The HIP paths against the float64 reference on the value ranges real inputs have (-m gpu): data scaled by 2^p down to where the max(pos + lambda, eps)
+guard of nmf.m:168,199 / cnmf.m:193,231 decides the update (and up to 2^40), a 12-decade spectral tilt over the rows of V, exact zeros in V, exact zeros
+in W_init and H_init.  The inputs and the table of calls, shapes and paths are tests/regime_inputs.py; tests/test_regime_inputs_host.py shows on the CPU that
+the reference is finite on every case, that the guard is as active as the case's name says and that nothing an fp32 path forms leaves fp32's normal range.
+
+Bars: the project contract -- relative Frobenius error <= 1e-5 on W and on H, <= 1e-6 on a finite cost (1e-5 for is, as in tests/test_gpu_parity.py), the
+same NaN / Inf pattern on a non-finite one, identical cost lengths.  The float64 drivers keep the bars of their own files, imported from there: the
+float64 mode of nmf (tests/test_gpu_nmf64.py: 1e-10, 1e-11 on the cost) and cnmf_batch (tests/test_gpu_cnmf_batch.py: 1e-9).  nmf_batch runs on the same
+float64 pass kernel as cnmf_batch (csrc/nb_pass.h) and is held to the same 1e-9 here: its own file states the contract because its V is not
+fp32-representable, and these V are -- a factor 2^p keeps them so --, so the derivation in tests/test_gpu_cnmf_batch.py applies (sums of at most 257 terms,
+6 iterations).  Besides the exponents that reach the W-step guard, is runs at p = +57 (regime_inputs.IS_HGUARD_P), where the H-step copies of the guard
+decide, without and with lambda = 2^-54 (the row with m = 64 is the one whose H update runs in the fused kernel's own epilogue).  zeros_wh: a zero of the reference is an exact zero of the result, and nothing is NaN.  zeros_v: W and H
+are finite.  tilted: the largest PER-ROW relative error of W (per column of H) is at most the contract times regime_inputs.TILT_RATIO, the ratio by which
+the reference itself is more sensitive per row on tilted data than on untilted data -- the Frobenius norm is blind to the quiet rows, whose norms are
+1e-11 of the loud ones'."""
+import numpy as np
+import pytest
+
+import regime_inputs as R
+import regime_oracle as RO
+import test_gpu_cnmf_batch as TCB
+import test_gpu_nmf64 as T64
+from conftest import record_err, rel_fro
+
+pytestmark = pytest.mark.gpu
+
+max_rel = lambda c, c0: float(np.max(np.abs(c - c0) / np.abs(c0)))
+# row -> (bar on W and H, bar on the cost for euclidean / kl, for is, how the cost error is measured)
+BARS = {"nmf_f64": (T64.TOL_WH, T64.TOL_COST, T64.TOL_COST, max_rel), "nmf_batch": (TCB.TOL, TCB.TOL, TCB.TOL, max_rel),
+        "cnmf_batch": (TCB.TOL, TCB.TOL, TCB.TOL, max_rel)}
+CONTRACT = (1e-5, 1e-6, 1e-5, rel_fro)
+
+
+def _run(lib, row, probs, div, lam):
+    """the library call of a row on the problems of a case -> [(W, H, cost) per problem]"""
+    r = R.ROWS[row]
+    cfg = dict(r["cfg"], divergence=div, maxiter=R.ITERS, tolerance=R.NO_STOP, nmfx_disable_stop=True)
+    if lam:
+        cfg.update(W_sparsity=lam, H_sparsity=lam)
+    call, K = r["call"], probs[0][2].shape[0]
+    if call in ("nmf_batch", "cnmf_batch"):
+        cfg.update(W_init=[p[1] for p in probs], H_init=[p[2] for p in probs])
+        Vs = [p[0] for p in probs]
+        W, H, c = lib.nmf_batch(Vs, K, cfg) if call == "nmf_batch" else lib.cnmf_batch(Vs, K, probs[0][1].shape[2], cfg)
+        return list(zip(W, H, c))
+    V, W0, H0 = probs[0]
+    cfg.update(W_init=W0, H_init=H0)
+    if call == "nmf":
+        return [lib.nmf(V, K, cfg)]
+    if call == "cnmf":
+        return [lib.cnmf(V, K, W0.shape[2], cfg)]
+    if call == "wnmf":
+        return [lib.wnmf(V, R.weights(row), K, cfg)]
+    return [lib.wcnmf(V, R.weights(row), K, W0.shape[2], cfg)]
+
+
+@pytest.mark.parametrize("case", R.cases(), ids=R.case_id)
+def test_regime(gpu_lib, case):
+    row, family, div, tag = case
+    probs, lam = R.problems(row, family, div, tag)
+    refs = RO.reference(row, family, div, tag)
+    with np.errstate(all="ignore"):
+        gots = _run(gpu_lib, row, probs, div, lam)
+    tol_wh, tol_cost, tol_cost_is, cost_err = BARS.get(row, CONTRACT)
+    tol_cost = tol_cost_is if div == "is" else tol_cost
+    sfx = "_f64" if row in ("nmf_f64", "nmf_batch", "cnmf_batch") else ""      # the float64 drivers' figures are kept apart from the fp32 paths'
+    rec = lambda **kw: record_err(**{"%s_%s%s" % (family, k, sfx): v for k, v in kw.items()})
+    assert len(gots) == len(refs)
+    failures = []
+    for b, ((W, H, c), (W0, H0, c0)) in enumerate(zip(gots, refs)):
+        W, H, c = np.asarray(W, dtype=np.float64), np.asarray(H, dtype=np.float64), np.asarray(c, dtype=np.float64)
+        assert W.shape == W0.shape and H.shape == H0.shape and len(c) == len(c0) == R.ITERS
+        e = rec(W=rel_fro(W, W0), H=rel_fro(H, H0))
+        if np.all(np.isfinite(c0)):
+            e.update(rec(cost=cost_err(c, c0) if np.all(np.isfinite(c)) else np.inf))
+        if family == "tilted":
+            e.update(rec(W_row=RO.per_row(W, W0), H_col=RO.per_col(H, H0)))
+        print(R.case_id(case), b, e)
+        # every figure is recorded before anything is asserted
+        ok = lambda name, bar: failures.append((b, name, e[name], bar)) if not e[name] <= bar else None
+        for name in e:
+            kind = name[len(family) + 1:len(name) - len(sfx)]
+            if kind in ("W", "H"):
+                ok(name, tol_wh)
+            elif kind == "cost":
+                ok(name, tol_cost)
+            else:
+                ok(name, tol_wh * R.TILT_RATIO[(R.key(row), div)][kind == "H_col"])
+        if not np.all(np.isfinite(c0)):      # the same NaN / +-Inf pattern
+            if not (np.array_equal(np.isnan(c), np.isnan(c0)) and np.array_equal(c[~np.isnan(c0)], c0[~np.isnan(c0)])):
+                failures.append((b, "cost pattern", c, c0))
+        if family == "zeros_v" and not (np.all(np.isfinite(W)) and np.all(np.isfinite(H))):
+            failures.append((b, "non-finite W or H"))
+        if family == "zeros_wh":
+            if np.isnan(W).any() or np.isnan(H).any() or np.isnan(c).any():
+                failures.append((b, "NaN"))
+            if not (np.array_equal(W == 0, W0 == 0) and np.array_equal(H == 0, H0 == 0)):
+                failures.append((b, "zeros moved", int(np.sum((W == 0) != (W0 == 0))), int(np.sum((H == 0) != (H0 == 0)))))
+    assert not failures, failures
