@@ -251,6 +251,21 @@ nmfx_status nmfx_nmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *
  * NMFX_ERR_NOMEM with the byte count.  nmfx_last_call_timing describes the call. */
 nmfx_status nmfx_cnmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *col_offsets /* batch + 1, col_offsets[0] = 0, increasing */,
                             nmfx_result *r, int32_t *cost_len /* batch */);
+/* `batch` independent weighted nmf problems in one call: nmfx_nmf_batch's layouts, arithmetic and rules, with nmfx_wnmf's weights.  M (m x N, p->dtype,
+ * column-major, >= 0 and finite, the problems side by side like p->V) weights every element of the data fit; with S = W_b*H_b, on = M > 0:
+ *   euclidean  A = on ? M.*V : 0,  B = on ? M.*S : 0;   kl  A = on ? M.*V./S : 0,  B = on ? M : 0;   cost = sum(on ? M.*d(V, S) : 0) + the L1 terms
+ * the W step contracts A*H_b' and B*H_b', the H step W_b'*A and W_b'*B.  The maps select on M: where M == 0 the entry contributes exactly 0 and V is never
+ * looked at there (NaN, Inf and negative values are carried along).  Result b is what nmfx_wnmf computes for problem b alone, in float64; with M == 1
+ * everywhere it is nmfx_nmf_batch's.  A new entry point; no structure grows, so NMFX_VERSION stays 600.
+ *   p->V, M  m x N;  p->H_init, r->H  K_total x N;  p->W_init, r->W  m x K_total x batch;  r->cost  maxiter x batch, column-major;  cost_len  out [batch]
+ * T and num_sources must be 1; divergence is euclidean or kl (is / ab: NMFX_ERR_UNSUPPORTED, as are n_gpus > 1, multi_backend != 0 and K_total > 256); a
+ * NULL M is NMFX_ERR_INVALID; tolerance < 0 disables the stop rule; path is ignored.  Device arithmetic: V and M are kept as fp32, everything else is
+ * float64 (v_mfma_f64_16x16x4_f64); no sum that reaches a result uses an atomic, and a problem's result does not depend on its place in the batch.
+ * Device memory: 8*m*N (V and M) + 8*K*N (H) + 16*m*K*batch (W and its transposed copy) + 16*64*KP bytes per (64 rows, 256 columns) of every problem
+ * (KP = K rounded up to 32, 64, 128 or 256; both divergences keep two slabs) + 8*maxiter*batch, and 8*K*N more with K > 128; a failed allocation is
+ * NMFX_ERR_NOMEM with the byte count.  nmfx_last_call_timing describes the call. */
+nmfx_status nmfx_wnmf_batch(const nmfx_problem *p, const void *M, int32_t batch, const int64_t *col_offsets /* batch + 1, col_offsets[0] = 0, increasing */,
+                            nmfx_result *r, int32_t *cost_len /* batch */);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,

@@ -1,4 +1,4 @@
-// The pass kernel, the decide kernel and the host helpers that nmf_batch.hip and cnmf_batch.hip share.  Included once by each of the two
+// The pass kernel, the decide kernel and the host helpers that nmf_batch.hip, cnmf_batch.hip and wnmf_batch.hip share.  Included once by each of the three
 // translation units; everything lives in an anonymous namespace, so each gets its own instantiations.  The block reduction is dev_reduce.h's and the float64
 // staging (ingest64 / egress64) api_common.h's, as in the other add-on drivers; grid_of (a workgroup per item) is this pair's own.
 #pragma once
@@ -45,6 +45,7 @@ struct NbPass {
     const double *cw;       // H step, KL: colsum(W_b) [b][k]
     double *Pbuf;           // H step, euclidean at the widest K: W_b'*S of the first of its two launches, K x N
     double lamH;
+    const float *M;         // WGT: the weights, m x N beside V
 };
 
 // WHICH: 0 = everything in one launch.  The euclidean step has two contractions of the second kind (A = V and A = S); at KP = 256 their accumulators alone would
@@ -54,13 +55,19 @@ struct NbPass {
 // CONV (cnmf_batch.hip): the H-side operand is the overlapping WINDOW of H, row j = the K*T contiguous doubles H[:, j-T+1 .. j] of the column-major
 // H (stride Kb), element kappa read as zero -- and never loaded: it is the neighbouring problem's, or lies before the allocation -- where kappa < (T-1-j)*Kb.
 // The W-side operand is WC[b][i][kappa], kappa = (T-1-t)*Kb + k.  The H step stores O = WC'*A (and WC'*S) to Qbuf (Pbuf) instead of updating H.
-template <int KP, int DIV, bool HS, int WHICH, bool CONV>
+//
+// WGT (wnmf_batch.hip): a weight M(c, r) >= 0 per entry of V, loaded with V's access pattern; on = M > 0 SELECTS, so that V is never looked at
+// where M == 0.  Euclidean: A = on ? M*V : 0 and the second operand on ? M*S : 0.  KL: A = on ? M*V/S : 0 and a second operand on ? M : 0 where the unweighted
+// step has none, so KL carries both accumulator sets, takes the WHICH = 1 / 2 split and the doubled slab like the euclidean step, and its H-step epilogue
+// reads its denominators from the second accumulator (Pbuf) instead of colsum(W); its denominators-only launch (WHICH = 1) forms no S at all.
+template <int KP, int DIV, bool HS, int WHICH, bool CONV, bool WGT = false>
 __global__ __launch_bounds__(256) void nb_pass(const NbPass g) {
     constexpr int LDY = KP + 4, NKB = KP / 16, NKK = KP / 4;
     constexpr int NCB = nb_ncb(KP), TS = 16 * NCB;   // streamed rows per LDS stage
-    constexpr bool DO_N = WHICH != 1, DO_P = DIV == NB_EUC && WHICH != 2, COST = !HS && DO_N;
-    constexpr bool NEED_S = DIV == NB_KL || DO_P || COST;
-    static_assert(DIV == NB_EUC || WHICH == 0, "KL has one contraction");
+    constexpr bool DO_N = WHICH != 1, DO_P = (DIV == NB_EUC || WGT) && WHICH != 2, COST = !HS && DO_N;
+    constexpr bool NEED_S = (DIV == NB_KL && DO_N) || (DIV == NB_EUC && DO_P) || COST;
+    static_assert(DIV == NB_EUC || WHICH == 0 || WGT, "KL has one contraction");
+    static_assert(!(WGT && CONV), "the convolutive passes have no weights");
     extern __shared__ __align__(16) double Ys[];   // [TS][LDY]
     __shared__ double sh[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;
@@ -85,6 +92,7 @@ __global__ __launch_bounds__(256) void nb_pass(const NbPass g) {
         const long T1 = CONV ? g.T - 1 : 0;
         const double *Hb = g.Hm + pb.col0 * Kb;
         const float *Vb = g.V + m * pb.col0;
+        const float *Mb = WGT ? g.M + m * pb.col0 : nullptr;
         const long r = r0 + 16 * wv + l15;
         const bool rok = r < R;
         // the stationary rows as MFMA operands: lane (l15, lg) holds X(r, 4 kk + lg)
@@ -122,6 +130,16 @@ __global__ __launch_bounds__(256) void nb_pass(const NbPass g) {
                     const bool ok = rok && c < cend;
                     vv[cb][e] = ok ? (HS ? Vb[c + m * r] : Vb[r + m * c]) : 1.f;
                 }
+            f32x4 mm[WGT ? NCB : 1];
+            if constexpr (WGT) {
+#pragma unroll
+                for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const long c = c0 + 16 * cb + 4 * e + lg;
+                        mm[cb][e] = (rok && c < cend) ? (HS ? Mb[c + m * r] : Mb[r + m * c]) : 0.f;   // (outside the problem: weight 0)
+                    }
+            }
             __syncthreads();
             f64x4 S[NCB];
 #pragma unroll
@@ -142,6 +160,19 @@ __global__ __launch_bounds__(256) void nb_pass(const NbPass g) {
                     const long c = c0 + 16 * cb + 4 * e + lg;
                     const bool ok = rok && c < cend;
                     const double s = S[cb][e], v = (double)vv[cb][e];
+                    if constexpr (WGT) {
+                        const double w = (double)mm[cb][e];
+                        const bool on = w > 0.0;   // (false outside the problem)
+                        if constexpr (COST) {
+                            if (on) {
+                                if constexpr (DIV == NB_EUC) { const double d = v - s; part += w * (d * d); }
+                                else part += w * ((v * log(v / s) - v) + s);
+                            }
+                        }
+                        if constexpr (DIV == NB_EUC) { A[cb][e] = on ? w * v : 0.0; S[cb][e] = on ? w * s : 0.0; }
+                        else { A[cb][e] = on ? (w * v) / s : 0.0; S[cb][e] = on ? w : 0.0; }
+                        continue;
+                    }
                     if constexpr (COST) {
                         if (ok) {
                             if constexpr (DIV == NB_EUC) { const double d = v - s; part += d * d; }       // nmf.m:208
@@ -166,7 +197,7 @@ __global__ __launch_bounds__(256) void nb_pass(const NbPass g) {
         }
         if constexpr (!HS) {
             if (!g.cost_only) {
-                double *sl = g.slab + (long)item * ((DIV == NB_EUC ? 2 : 1) * KP * NB_T) + 16 * wv + l15;
+                double *sl = g.slab + (long)item * ((DIV == NB_EUC || WGT ? 2 : 1) * KP * NB_T) + 16 * wv + l15;
 #pragma unroll
                 for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
@@ -196,7 +227,7 @@ __global__ __launch_bounds__(256) void nb_pass(const NbPass g) {
                         } else if constexpr (WHICH == 1) g.Pbuf[base + k] = accP[kb][e];
                         else {
                             double pos;
-                            if constexpr (DIV == NB_KL) pos = g.cw[(long)b * K + k];
+                            if constexpr (DIV == NB_KL && !WGT) pos = g.cw[(long)b * K + k];
                             else if constexpr (WHICH == 2) pos = g.Pbuf[base + k];
                             else pos = accP[kb][e];
                             g.Hm[base + k] = g.Hm[base + k] * (accN[kb][e] / fmax(pos + g.lamH, EPS64));
@@ -207,34 +238,35 @@ __global__ __launch_bounds__(256) void nb_pass(const NbPass g) {
     }
 }
 
-template <int KP, int DIV, bool HS, int WHICH, bool CONV>
+template <int KP, int DIV, bool HS, int WHICH, bool CONV, bool WGT = false>
 nmfx_status nb_launch(hipStream_t st, const NbPass &g) {
     constexpr int lds = 16 * nb_ncb(KP) * (KP + 4) * 8;
     static LdsAttrOnce attr;
-    TRY(attr.set(reinterpret_cast<const void *>(&nb_pass<KP, DIV, HS, WHICH, CONV>), lds));
+    TRY(attr.set(reinterpret_cast<const void *>(&nb_pass<KP, DIV, HS, WHICH, CONV, WGT>), lds));
     const unsigned grid = (unsigned)std::min(g.items, NB_MAX_GRID);
-    hipLaunchKernelGGL((nb_pass<KP, DIV, HS, WHICH, CONV>), dim3(grid), dim3(256), lds, st, g);
+    hipLaunchKernelGGL((nb_pass<KP, DIV, HS, WHICH, CONV, WGT>), dim3(grid), dim3(256), lds, st, g);
     NMFX_HIP(hipGetLastError());
     return NMFX_OK;
 }
 int nb_kp(int K) { return K <= 32 ? 32 : (K <= 64 ? 64 : (K <= 128 ? 128 : 256)); }
-template <int DIV, bool HS, bool CONV>
+constexpr bool nb_two_launches(int KP, bool two_sets) { return two_sets && KP == 256; }   // two accumulator sets (euclidean; WGT: kl too) at the widest K: WHICH = 1, then 2
+template <int DIV, bool HS, bool CONV, bool WGT = false>
 nmfx_status nb_launch_k(hipStream_t st, const NbPass &g) {
     switch (nb_kp(g.K)) {
-        case 32: return nb_launch<32, DIV, HS, 0, CONV>(st, g);
-        case 64: return nb_launch<64, DIV, HS, 0, CONV>(st, g);
-        case 128: return nb_launch<128, DIV, HS, 0, CONV>(st, g);
+        case 32: return nb_launch<32, DIV, HS, 0, CONV, WGT>(st, g);
+        case 64: return nb_launch<64, DIV, HS, 0, CONV, WGT>(st, g);
+        case 128: return nb_launch<128, DIV, HS, 0, CONV, WGT>(st, g);
         default:
-            if constexpr (DIV == NB_EUC) {
-                if (!g.cost_only) TRY((nb_launch<256, DIV, HS, 1, CONV>(st, g)));
-                return nb_launch<256, DIV, HS, 2, CONV>(st, g);
-            } else return nb_launch<256, DIV, HS, 0, CONV>(st, g);
+            if constexpr (nb_two_launches(256, DIV == NB_EUC || WGT)) {
+                if (!g.cost_only) TRY((nb_launch<256, DIV, HS, 1, CONV, WGT>(st, g)));
+                return nb_launch<256, DIV, HS, 2, CONV, WGT>(st, g);
+            } else return nb_launch<256, DIV, HS, 0, CONV, WGT>(st, g);
     }
 }
-template <bool CONV>
+template <bool CONV, bool WGT = false>
 nmfx_status nb_run_pass(hipStream_t st, const NbPass &g, int div, bool hstep) {
-    if (div == NB_EUC) return hstep ? nb_launch_k<NB_EUC, true, CONV>(st, g) : nb_launch_k<NB_EUC, false, CONV>(st, g);
-    return hstep ? nb_launch_k<NB_KL, true, CONV>(st, g) : nb_launch_k<NB_KL, false, CONV>(st, g);
+    if (div == NB_EUC) return hstep ? nb_launch_k<NB_EUC, true, CONV, WGT>(st, g) : nb_launch_k<NB_EUC, false, CONV, WGT>(st, g);
+    return hstep ? nb_launch_k<NB_KL, true, CONV, WGT>(st, g) : nb_launch_k<NB_KL, false, CONV, WGT>(st, g);
 }
 
 struct NbDecide {

@@ -15,6 +15,7 @@
     W, H, cost = cnmf_batch(Vs, num_basis_elems, context_len, config)   cnmf.m:1 per problem (lists: B independent problems in one call)
     W, H, cost = wnmf(V, M, num_basis_elems, config)              nmf.m:1 with per-entry weights M >= 0 (missing or unreliable data)
     W, H, cost = wcnmf(V, M, num_basis_elems, context_len, config)   cnmf.m:1 with per-entry weights M >= 0
+    W, H, cost = wnmf_batch(Vs, Ms, num_basis_elems, config)      wnmf per problem (lists: B independent weighted problems in one call)
 
 Same argument meaning, defaults and error behaviour as the MATLAB functions (a MATLAB cell array is
 a Python list, a struct a dict; errors are ValueError carrying the reference's message).  This file
@@ -276,20 +277,26 @@ def _weighted_inputs(fn, V, M, config):
     V = _as_data(V)
     if V.ndim != 2:
         raise ValueError("%s: V must be a matrix" % fn)
+    return V, _weights(fn, M, V.shape, V.dtype), div
+
+
+def _weights(fn, M, shape, dtype, name="M", of="V"):
+    """The weight rules of wnmf, wcnmf and wnmf_batch: `name` has the shape of `of`, is of a real kind and every weight is >= 0 and finite, also in
+    the dtype it travels in.  Returns it in that dtype, column-major."""
     M = np.asarray(M)
-    if M.shape != V.shape:
-        raise ValueError("%s: M must have the shape of V, %r; got %r" % (fn, V.shape, M.shape))
+    if M.shape != shape:
+        raise ValueError("%s: %s must have the shape of %s, %r; got %r" % (fn, name, of, shape, M.shape))
     if M.dtype.kind not in "buif":
-        raise ValueError("%s: M must be bool, integer or float; got %s" % (fn, M.dtype))
+        raise ValueError("%s: %s must be bool, integer or float; got %s" % (fn, name, M.dtype))
     if M.dtype.kind == "f" and not np.all(np.isfinite(M)):
-        raise ValueError("%s: every weight in M must be finite" % fn)
+        raise ValueError("%s: every weight in %s must be finite" % (fn, name))
     if M.dtype.kind in "if" and M.size and M.min() < 0:
-        raise ValueError("%s: every weight in M must be >= 0" % fn)
+        raise ValueError("%s: every weight in %s must be >= 0" % (fn, name))
     with np.errstate(over="ignore"):     # (a float64 weight beyond float32's range becomes Inf and is refused below)
-        Mf = _f_order(M, V.dtype)
+        Mf = _f_order(M, dtype)
     if not np.all(np.isfinite(Mf)):
-        raise ValueError("%s: every weight in M must be finite in V's dtype (%s)" % (fn, V.dtype))
-    return V, Mf, div
+        raise ValueError("%s: every weight in %s must be finite in %s's dtype (%s)" % (fn, name, of, np.dtype(dtype)))
+    return Mf
 
 
 def wnmf(V, M, num_basis_elems, config=None, device=0):
@@ -464,6 +471,129 @@ def nmf_batch(Vs, num_basis_elems, config=None, device=0):
     r = _lib.Result()
     r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
     _lib.check(_lib.load().nmfx_nmf_batch(C.byref(p), B, _fptr(off), C.byref(r), _fptr(lens)))
+    return ([np.array(Wout[:, :, b]) for b in range(B)], [np.array(Hout[:, off[b]:off[b + 1]]) for b in range(B)],
+            [cost[: lens[b], b].copy() for b in range(B)])
+
+
+def wnmf_batch(Vs, Ms, num_basis_elems, config=None, device=0):
+    """W, H, cost = wnmf_batch(Vs, Ms, num_basis_elems, config): B independent weighted nmf problems in one call -- three lists of length B, entry b being
+    what wnmf(Vs[b], Ms[b], num_basis_elems, config_b) computes: W[b] m-by-K, H[b] K-by-n_b, cost[b] trimmed by that problem's own stop rule.  Every
+    contraction runs in float64 on the device.
+
+    Ms is a list of B weight matrices, Ms[b] of the shape of Vs[b]; the weight rules are wnmf's (bool, integer or float; a negative or non-finite weight
+    is a ValueError) and so is the meaning: where Ms[b] == 0 the entry contributes exactly nothing and Vs[b] is never looked at there -- it may be NaN, Inf
+    or negative.  With Ms[b] == 1 everywhere problem b is nmf_batch's.  Everything else is nmf_batch's: the problems share the number of rows,
+    num_basis_elems (one positive integer: one source, at most 256) and the configuration, every Vs[b] has its own number of columns; float32 data stays
+    float32 when every Vs[b] is float32, anything else travels as float64, and the weights travel in that dtype; config takes nmf's keys with nmf's
+    defaults and clamping, each ONE value for the whole batch: divergence ('euclidean', 'kl' / 'kl_divergence'), W_sparsity, H_sparsity, W_fixed, H_fixed,
+    maxiter, tolerance, nmfx_disable_stop, seed / rng.  H_init is absent (empty) or a list of B matrices K-by-n_b; W_init is absent (empty), ONE m-by-K
+    matrix used for every problem (with W_fixed: one trained dictionary over a test set) or a list of B matrices.  Missing inits are drawn from the one
+    rng problem by problem, for each problem in nmf's order.
+
+    Refused with ValueError: everything nmf_batch refuses (the 'is' / 'ab' divergences included), Ms that is not a list of B arrays, a Ms[b] of another
+    shape than Vs[b] or of a non-real kind, and a weight that is negative or not finite.  nmfx_path is ignored (there is one path)."""
+    cfg = dict(config) if config else {}
+    try:
+        _precision(cfg, "wnmf_batch")
+    except ValueError as e:
+        raise ValueError(str(e) if "wnmf_batch" in str(e) else "wnmf_batch: %s" % e) from None
+    if cfg.get("nmfx_gpus", None) is not None or cfg.get("nmfx_multi_backend", None) is not None:
+        raise ValueError("wnmf_batch runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported")
+    if not _is_cell(Vs) or len(Vs) == 0:
+        raise ValueError("wnmf_batch: Vs must be a non-empty list of matrices")
+    Vs = [np.asarray(v) for v in Vs]
+    B = len(Vs)
+    for b, v in enumerate(Vs):
+        if v.ndim != 2:
+            raise ValueError("wnmf_batch: Vs[%d] must be a matrix" % b)
+        if v.shape[0] != Vs[0].shape[0]:
+            raise ValueError("wnmf_batch: Vs[%d] has %d rows, Vs[0] has %d: the problems of a batch share their rows" % (b, v.shape[0], Vs[0].shape[0]))
+        if v.shape[1] < 1 or v.shape[0] < 1:
+            raise ValueError("wnmf_batch: Vs[%d] is empty" % b)
+    if not _is_cell(Ms) or len(Ms) != B:
+        raise ValueError("wnmf_batch: Ms must be a list of %d weight matrices, one per problem" % B)
+    if _is_cell(num_basis_elems) or np.ndim(num_basis_elems) != 0:
+        raise ValueError("wnmf_batch: num_basis_elems must be one positive integer (the batch has one source)")
+    K = int(num_basis_elems)
+    if K != num_basis_elems or K <= 0:
+        raise ValueError("wnmf_batch: num_basis_elems must be a positive integer")
+    if K > 256:
+        raise ValueError("wnmf_batch: num_basis_elems = %d, at most 256 is supported" % K)
+    div = cfg.get("divergence", "euclidean")                       # nmf.m:250-252
+    if not isinstance(div, str) or div not in _DIV_BATCH:
+        raise ValueError("wnmf_batch has the euclidean and kl divergences only; got %r" % (div,))
+    dt = np.float32 if all(v.dtype == np.float32 for v in Vs) else np.float64
+    Ms = [_weights("wnmf_batch", M, Vs[b].shape, dt, "Ms[%d]" % b, "Vs[%d]" % b) for b, M in enumerate(Ms)]
+    m = Vs[0].shape[0]
+    ns = [v.shape[1] for v in Vs]
+    Hi, Wi = cfg.get("H_init", None), cfg.get("W_init", None)
+    if not _isempty(Hi):
+        if not _is_cell(Hi) or len(Hi) != B:
+            raise ValueError("wnmf_batch: H_init must be a list of %d matrices" % B)
+        Hi = [np.asarray(h) for h in Hi]
+        for b, h in enumerate(Hi):
+            if h.shape != (K, ns[b]):
+                raise ValueError("wnmf_batch: H_init[%d] must be %d-by-%d" % (b, K, ns[b]))
+    else:
+        Hi = None
+    if not _isempty(Wi):
+        if _is_cell(Wi):
+            if len(Wi) != B:
+                raise ValueError("wnmf_batch: W_init must be one %d-by-%d matrix or a list of %d of them" % (m, K, B))
+            Wi = [np.asarray(w) for w in Wi]
+        else:
+            Wi = [np.asarray(Wi)] * B
+        for b, w in enumerate(Wi):
+            if w.shape != (m, K):
+                raise ValueError("wnmf_batch: W_init%s must be %d-by-%d" % ("[%d]" % b if _is_cell(cfg["W_init"]) else "", m, K))
+    else:
+        Wi = None
+    nonneg = lambda x: max(float(x), 0.0)
+    lw = _per_source(cfg, "W_sparsity", 1, 0.0, nonneg, "sparsity levels")      # nmf.m:312-401, one source
+    lh = _per_source(cfg, "H_sparsity", 1, 0.0, nonneg, "sparsity levels")
+    fw = _per_source(cfg, "W_fixed", 1, False, bool, "update switches")
+    fh = _per_source(cfg, "H_fixed", 1, False, bool, "update switches")
+    maxiter = cfg.get("maxiter", None)
+    maxiter = 100 if maxiter is None or maxiter <= 0 else int(maxiter)          # nmf.m:404-406
+    tol = cfg.get("tolerance", None)
+    tol = 1e-3 if tol is None or tol <= 0 else float(tol)                       # nmf.m:409-411
+    rng = _rng(cfg)
+    off = np.zeros(B + 1, dtype=np.int64)
+    off[1:] = np.cumsum(ns)
+    N = int(off[B])
+    V_all = np.empty((m, N), order="F", dtype=dt)
+    M_all = np.empty((m, N), order="F", dtype=dt)
+    H_all = np.empty((K, N), order="F", dtype=dt)
+    W_all = np.empty((m, K, B), order="F", dtype=dt)
+    for b in range(B):
+        lo, hi = off[b], off[b + 1]
+        with np.errstate(invalid="ignore", over="ignore"):      # (what lies under a zero weight is carried along, never looked at)
+            V_all[:, lo:hi] = Vs[b]
+        M_all[:, lo:hi] = Ms[b]
+        H_all[:, lo:hi] = Hi[b] if Hi is not None else np.fmax(rng.rand(K, ns[b]), EPS)     # nmf.m:277
+        if Wi is not None:
+            W_all[:, :, b] = Wi[b]
+        else:                                                                              # nmf.m:298-299
+            w = np.fmax(rng.rand(m, K), EPS)
+            W_all[:, :, b] = w * (1.0 / np.sqrt(np.sum(w ** 2, axis=0)))[None, :]
+    Wout = np.zeros((m, K, B), order="F", dtype=dt)
+    Hout = np.zeros((K, N), order="F", dtype=dt)
+    cost = np.zeros((maxiter, B), order="F")
+    lens = np.zeros(B, dtype=np.int32)
+    lw, lh = np.asarray(lw, dtype=np.float64), np.asarray(lh, dtype=np.float64)
+    fw, fh = np.asarray(fw, dtype=np.uint8), np.asarray(fh, dtype=np.uint8)
+    p = _lib.Problem()
+    p.m, p.n, p.K_total, p.T, p.dtype = m, N, K, 1, (_lib.F32 if dt == np.float32 else _lib.F64)
+    p.V, p.W_init, p.H_init = _fptr(V_all), _fptr(W_all), _fptr(H_all)
+    p.divergence, p.alpha, p.beta = _DIV_BATCH[div], 1.0, 1.0
+    p.num_sources, p.K_s = 1, None
+    p.W_sparsity, p.H_sparsity, p.W_fixed, p.H_fixed = _fptr(lw), _fptr(lh), _fptr(fw), _fptr(fh)
+    p.maxiter = maxiter
+    p.tolerance = -1.0 if cfg.get("nmfx_disable_stop", False) else tol
+    p.device = int(device)
+    r = _lib.Result()
+    r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
+    _lib.check(_lib.load().nmfx_wnmf_batch(C.byref(p), _fptr(M_all), B, _fptr(off), C.byref(r), _fptr(lens)))
     return ([np.array(Wout[:, :, b]) for b in range(B)], [np.array(Hout[:, off[b]:off[b + 1]]) for b in range(B)],
             [cost[: lens[b], b].copy() for b in range(B)])
 
