@@ -5,10 +5,10 @@ of V, exact zeros in V, exact zeros in W_init and H_init.
 numpy.random.RandomState is a frozen legacy generator, so both test files regenerate the same arrays; the oracle is not imported here.  Every V is rounded
 to the nearest fp32 value and kept as float64 (a scale of 2^p keeps it representable): the device's fp32 copy of V is lossless and the tests measure the
 kernels, not the rounding of the input.  Every family takes (m, n, K[, T]) and returns V, W_init (m x K, or m x K x T), H_init; `b` numbers the problems
-of a batch (it moves the seed of V)."""
+of a batch (it moves the seed of V).  The add-on calls (ADDON_ROWS: lnmf, constrainednmf, nmfsc, cnmfsc, cmfwisa, wnmf_batch) take the same families through addon_problem."""
 import numpy as np
 
-from conftest import synth
+from conftest import EPS, synth
 
 ITERS = 6
 NO_STOP = 1e-300     # the oracle has no switch for its stop rule: a tolerance no decrease can be below
@@ -65,6 +65,103 @@ def zeros_wh(m, n, K, T=None, frac=0.4, b=0):
     return V, W0, H0
 
 
+# ---- what the add-on calls take besides V, W_init and H_init -------------------------------------------------------------------------------------------------
+def labels(row):
+    """constrainednmf: tests/test_gpu_parity.py::_labels(n, 5, 0.3, 5) -- five classes with non-consecutive ids, about 30 % of the samples unlabelled"""
+    n = ROWS[row]["shape"][1]
+    rs = np.random.RandomState(5)
+    lab = rs.randint(0, 5, size=n) * 2 + 3
+    lab[rs.rand(n) < 0.3] = -1
+    return lab
+
+
+def phases(row):
+    """cmfwisa: one independent uniform phase matrix per source (tests/cmfwisa_inputs.py::random_phases explains why the default P_init compares nothing)"""
+    import cmfwisa_inputs as CI
+    (m, n), Ks = ROWS[row]["shape"], ROWS[row]["Ks"]
+    return CI.random_phases(m, n, len(Ks), seed=sum(Ks))
+
+
+def _c64(V):
+    return V.astype(np.complex64).astype(np.complex128)
+
+
+def _tilt(m, decades):
+    return 10.0 ** (-decades * np.arange(m) / (m - 1.0))[:, None]
+
+
+def _zero_masks(shapes_w, shapes_h, frac, b):
+    """the seeded zero masks of zeros_wh over the factors of one or several sources: every component but the first of each source"""
+    rw, rh = np.random.RandomState(4000 + b), np.random.RandomState(4500 + b)
+    mws, mhs = [rw.rand(*s) < frac for s in shapes_w], [rh.rand(*s) < frac for s in shapes_h]
+    for mw, mh in zip(mws, mhs):
+        mw[(slice(None), 0) + (0,) * (mw.ndim - 2)] = False
+        mh[0, :] = False
+    return mws, mhs
+
+
+def cmfwisa_problem(m, n, Ks, family, p=0, tag="", b=0):
+    """V complex Gaussian (a rough spectrogram stand-in, as tests/cmfwisa_inputs.py::noisy) rounded to complex64 values, W_init and H_init = max(rand, eps) per
+    source (lists).  scaled: V and every H_init times 2^p; tilted: the rows of V; zeros_v: 30 % of V exactly 0; zeros_wh: 40 % zeros in every source's W and H,
+    the first component of each source positive (beta_i = W_i H_i ./ sum_j W_j H_j then has neither 0 / 0 nor a zero to divide |V_bar_i| by)"""
+    rs = np.random.RandomState(1000 + b)
+    V = _c64(rs.randn(m, n) + 1j * rs.randn(m, n))
+    W0 = [np.fmax(np.random.RandomState(10 + i).rand(m, K), EPS) for i, K in enumerate(Ks)]
+    H0 = [np.fmax(np.random.RandomState(20 + i).rand(K, n), EPS) for i, K in enumerate(Ks)]
+    if family == "scaled":
+        V, H0 = V * 2.0 ** p, [h * 2.0 ** p for h in H0]
+    elif family == "tilted":
+        V = _c64(V * _tilt(m, 0 if tag == "flat" else 12))
+    elif family == "zeros_v":
+        V[np.random.RandomState(3000 + b).rand(m, n) < 0.3] = 0.0
+        if tag == "rowcol":
+            V[m // 3, :] = 0.0
+            V[:, n // 2] = 0.0
+    elif family == "zeros_wh":
+        mws, mhs = _zero_masks([w.shape for w in W0], [h.shape for h in H0], 0.4, b)
+        for w, h, mw, mh in zip(W0, H0, mws, mhs):
+            w[mw] = 0.0
+            h[mh] = 0.0
+    return V, W0, H0
+
+
+def addon_problem(row, family, p, tag, m, n, K, T, b):
+    """(V, W_init, H_init) of a problem of an add-on row (constrainednmf: Z_init in the place of H_init, K x (unlabelled samples + classes)).  Only `scaled`
+    differs from the families above: it scales what reaches the guard of the call --
+        lnmf              H_init alone (the W-step denominator is the row sums of H; V and W do not enter it)
+        nmfsc, cnmfsc     W_init where W_sparsity = 0, H_init otherwise (V is divided by its maximum, nmfsc.m:62; a projected factor loses its scale)
+        constrainednmf    V and Z_init, as nmf; wnmf_batch: V and H_init, as nmf_batch"""
+    r = ROWS[row]
+    call = r["call"]
+    if call == "cmfwisa":
+        return cmfwisa_problem(m, n, K, family, p, tag, b)
+    if family == "scaled":
+        if call in ("constrainednmf", "wnmf_batch"):
+            V, W0, H0 = scaled(m, n, K, T, p=p, b=b)
+        else:
+            V, W0, H0 = _base(m, n, K, T, b)
+            if call == "lnmf" or r["sc"][0] > 0:
+                H0 = H0 * 2.0 ** p
+            else:
+                W0 = W0 * 2.0 ** p
+    elif family == "tilted":
+        V, W0, H0 = tilted(m, n, K, T, decades=0 if tag == "flat" else 12, b=b)
+    elif family == "zeros_v":
+        V, W0, H0 = zeros_v(m, n, K, T, rowcol=(tag == "rowcol"), b=b)
+    else:
+        V, W0, H0 = zeros_wh(m, n, K, T, b=b)
+    if call == "constrainednmf":
+        lab = labels(row)
+        nz = int(np.count_nonzero(lab == -1)) + len(np.unique(lab[lab >= 0]))
+        Z0 = np.fmax(np.random.RandomState(9).rand(K, nz), EPS)
+        if family == "scaled":
+            Z0 = Z0 * 2.0 ** p
+        elif family == "zeros_wh":
+            Z0[_zero_masks([W0.shape], [Z0.shape], 0.4, b)[1][0]] = 0.0
+        H0 = Z0
+    return V, W0, H0
+
+
 # ---- the cases: which call, which shape, which path -------------------------------------------------------------------------------------------------
 # call: the library entry; shape: (m, n, K) or (m, n, K, T), for the batch calls (m, K[, T]) with the n_b in `ns`; cfg: what selects the path;
 # divs: the divergences the call has; weights: None, "unit" or "random" (the weights of tests/wnmf_inputs.py / tests/wcnmf_inputs.py)
@@ -93,16 +190,59 @@ ROWS = {
     "wnmf_random": dict(call="wnmf", shape=(129, 200, 33), cfg={}, divs=_ALL, weights="random"),
     "wcnmf_unit": dict(call="wcnmf", shape=(70, 90, 5, 4), cfg={}, divs=_ALL, weights="unit"),
     "wcnmf_random": dict(call="wcnmf", shape=(70, 90, 5, 4), cfg={}, divs=_ALL, weights="random"),
+    # ---- the calls with guard copies of their own (ADDON_CALLS below).  once: the call re-balances after one step, so the guard is reached in the first iteration only
+    # lnmf.m:69, W .* (N ./ max(P, eps)) with P = ones * H': the row sums of H.  One cost, the kl one (lnmf.m:81): the cases carry "kl"
+    "lnmf_generic": dict(call="lnmf", shape=(96, 130, 7), cfg=dict(nmfx_path=1), divs=("kl",), once=True),
+    "lnmf_fused_k32": dict(call="lnmf", shape=(129, 131, 32), cfg=dict(nmfx_path=2), divs=("kl",), once=True),
+    "lnmf_padded_k7": dict(call="lnmf", shape=(96, 130, 7), cfg={}, divs=("kl",), once=True),      # the default plan pads K = 7 to 32
+    # constrainednmf.m:207,235: labels as in tests/test_gpu_parity.py::_labels (some unlabelled, non-consecutive ids), Z_init given
+    "constrainednmf_generic": dict(call="constrainednmf", shape=(96, 130, 7), cfg=dict(nmfx_path=1), divs=_ALL),
+    "constrainednmf_fused_k32": dict(call="constrainednmf", shape=(129, 131, 32), cfg=dict(nmfx_path=2), divs=_ALL),
+    # nmfsc.m:182,232.  sc = (W_sparsity, H_sparsity): (0, 0) both steps multiplicative, (0.4, 0) the H step only, (0, 0.5) the W step only.  m * n * K <= 2^27
+    # with no path asked for runs in float64 end to end (sc64.hip::nmfsc_f64_eligible); nmfx_path = 1 keeps the same shape on the fp32 path (aux.hip::mu_update).
+    # guard: the step whose guard the scaled exponents are chosen for
+    # NOTE: with sc = (0.4, 0) the reference ends its first W line search by step-size underflow (nmfsc.m:221-225) on every input here, H_init with unit rows
+    # included: the `w4` rows compare that one H step and the initial cost, not six iterations
+    "nmfsc_f64_00": dict(call="nmfsc", shape=(96, 130, 7), cfg={}, divs=_ALL[:1], sc=(0.0, 0.0), guard="H", once=True),
+    "nmfsc_f64_w4": dict(call="nmfsc", shape=(96, 130, 7), cfg={}, divs=_ALL[:1], sc=(0.4, 0.0), guard="H", once=True),
+    "nmfsc_f64_h5": dict(call="nmfsc", shape=(96, 130, 7), cfg={}, divs=_ALL[:1], sc=(0.0, 0.5), guard="W", once=True),
+    "nmfsc_f32_00": dict(call="nmfsc", shape=(96, 130, 7), cfg=dict(nmfx_path=1), divs=_ALL[:1], sc=(0.0, 0.0), guard="H", once=True),
+    "nmfsc_f32_w4": dict(call="nmfsc", shape=(96, 130, 7), cfg=dict(nmfx_path=1), divs=_ALL[:1], sc=(0.4, 0.0), guard="H", once=True),
+    "nmfsc_f32_h5": dict(call="nmfsc", shape=(96, 130, 7), cfg=dict(nmfx_path=1), divs=_ALL[:1], sc=(0.0, 0.5), guard="W", once=True),
+    # cnmfsc.m:202 (H .* neg ./ (pos + eps): plus, not max) with H_sparsity = 0, and cnmfsc.m:261 with W_sparsity = 0 on its two slice kernels: nmfx_path = 1 updates
+    # slice by slice (aux.hip::mu_plain_diff), the fused passes (K = 32 / 64 / 128, an instantiated (K, T), m and n >= 64, m % 4 == 0) run the slice loop in one
+    # launch (aux.hip::cnmfsc_w_slices).  With H_sparsity = 0 the H step re-scales W before the W step can reach its guard, so the W-guard rows keep H sparse
+    "cnmfsc_generic_00": dict(call="cnmfsc", shape=(96, 130, 7, 3), cfg=dict(nmfx_path=1), divs=_ALL[:1], sc=(0.0, 0.0), guard="H", once=True),
+    "cnmfsc_fused_00": dict(call="cnmfsc", shape=(132, 131, 32, 3), cfg=dict(nmfx_path=2), divs=_ALL[:1], sc=(0.0, 0.0), guard="H", once=True),
+    "cnmfsc_generic_h5": dict(call="cnmfsc", shape=(96, 130, 7, 3), cfg=dict(nmfx_path=1), divs=_ALL[:1], sc=(0.0, 0.5), guard="W", once=True),
+    "cnmfsc_fused_h5": dict(call="cnmfsc", shape=(132, 131, 32, 3), cfg=dict(nmfx_path=2), divs=_ALL[:1], sc=(0.0, 0.5), guard="W", once=True),
+    # cmfwisa.m:190-202: shape = (m, n), Ks per source; distinct random phases per source (tests/cmfwisa_inputs.py::random_phases).  Two sources take the fused E
+    # pass, nmfx_path = 1 and five sources (past CMF_FUSED_MAX_I) the generic one; 65 x 130 with Ks = (5, 3): odd K_i and edge tiles in both directions
+    "cmfwisa_fused_i2": dict(call="cmfwisa", shape=(64, 96), Ks=(5, 8), cfg={}, divs=_ALL[:1]),
+    "cmfwisa_generic_i2": dict(call="cmfwisa", shape=(64, 96), Ks=(5, 8), cfg=dict(nmfx_path=1), divs=_ALL[:1]),
+    "cmfwisa_generic_i5": dict(call="cmfwisa", shape=(64, 96), Ks=(2, 3, 2, 4, 3), cfg={}, divs=_ALL[:1]),
+    "cmfwisa_ragged": dict(call="cmfwisa", shape=(65, 130), Ks=(5, 3), cfg={}, divs=_ALL[:1]),
+    # wnmf_batch_inputs.PARITY["edges"] with the weights of tests/wnmf_batch_inputs.py; n_b = 9 for 1 and 5 under zeros_v / zeros_wh as in the nmf_batch row
+    "wnmf_batch_mask": dict(call="wnmf_batch", shape=(70, 5), ns=(1, 5, 63, 64, 65, 130, 257), ns_zeros=(9, 63, 64, 65, 130, 257), cfg={}, divs=_ALL[:2], weights="mask"),
+    "wnmf_batch_weights": dict(call="wnmf_batch", shape=(70, 5), ns=(1, 5, 63, 64, 65, 130, 257), ns_zeros=(9, 63, 64, 65, 130, 257), cfg={}, divs=_ALL[:2], weights="weights"),
 }
+ADDON_CALLS = ("lnmf", "constrainednmf", "nmfsc", "cnmfsc", "cmfwisa", "wnmf_batch")
+ADDON_ROWS = tuple(r for r in ROWS if ROWS[r]["call"] in ADDON_CALLS)
 SCALED_ROWS = tuple(ROWS)
 OTHER_ROWS = tuple(r for r in ROWS if ROWS[r]["call"] in ("nmf", "cnmf", "nmf_batch"))      # tilted, zeros_v, zeros_wh
 ZEROS_V_ROWS = OTHER_ROWS + ("wnmf_unit",)
+ADDON_TILTED_ROWS = tuple(r for r in ADDON_ROWS if ROWS[r]["call"] in ("lnmf", "constrainednmf", "cmfwisa"))
+# the all-zero row and column of V, euclidean: the reference stays finite on every add-on call that has a euclidean cost (lnmf has none)
+ADDON_ROWCOL_ROWS = tuple(r for r in ADDON_ROWS if ROWS[r]["call"] != "lnmf")
+EXTRAS = {"constrainednmf": ("Z",), "cmfwisa": ("P", "V_hat")}      # what an add-on call returns besides W, H and the cost
 
 
 def shapes(row, family="scaled"):
     """the (m, n, K, T) of every problem of a row (T = None: no context); one problem unless the call is a batch"""
     r = ROWS[row]
     s = r["shape"]
+    if r["call"] == "cmfwisa":
+        return [(s[0], s[1], r["Ks"], None)]
     if "ns" in r:
         ns = r.get("ns_zeros", r["ns"]) if family in ("zeros_v", "zeros_wh") else r["ns"]
         return [(s[0], n, s[1], s[2] if len(s) > 2 else None) for n in ns]
@@ -112,15 +252,20 @@ def shapes(row, family="scaled"):
 def key(row):
     """what the reference of a row depends on (rows that differ in the path alone share it): the keys of SCALED_P and TILT_RATIO"""
     r = ROWS[row]
-    call = {"nmf_batch": "nmfbatch", "cnmf_batch": "cnmfbatch"}.get(r["call"], r["call"])
-    return "_".join([call, "x".join(str(d) for d in r["shape"])] + ([r["weights"]] if r.get("weights") else []))
+    call = {"nmf_batch": "nmfbatch", "cnmf_batch": "cnmfbatch", "wnmf_batch": "wnmfbatch"}.get(r["call"], r["call"])
+    more = ([r["weights"]] if r.get("weights") else []) + (["+".join(str(k) for k in r["Ks"])] if "Ks" in r else []) + (["sW%g_sH%g" % r["sc"]] if "sc" in r else [])
+    return "_".join([call, "x".join(str(d) for d in r["shape"])] + more)
 
 
-def weights(row):
-    """the weights M of a weighted row (None otherwise): all ones, or what tests/wnmf_inputs.py::weights(m, n, "weights") draws"""
+def weights(row, family="scaled"):
+    """the weights M of a weighted row (None otherwise): all ones, or what tests/wnmf_inputs.py::weights(m, n, "weights") draws; for wnmf_batch the list of
+    tests/wnmf_batch_inputs.py::weights(b, m, n_b, kind) over the problems of the family"""
     kind = ROWS[row].get("weights")
     if kind is None:
         return None
+    if ROWS[row]["call"] == "wnmf_batch":
+        import wnmf_batch_inputs as WB
+        return [WB.weights(b, m, n, kind) for b, (m, n, K, T) in enumerate(shapes(row, family))]
     m, n = ROWS[row]["shape"][:2]
     if kind == "unit":
         return np.ones((m, n))
@@ -169,6 +314,36 @@ SCALED_P = {
     ("wcnmf_70x90x5x4_unit", "kl"): (-56, -62),
     ("wcnmf_70x90x5x4_random", "euclidean"): (-28, -31),
     ("wcnmf_70x90x5x4_random", "kl"): (-56, -61),
+    # lnmf: H_init alone is scaled, and the guard acts on the K row sums of H in the first iteration only (the H step re-balances): mixed = 5 of 7 / 12 of 32 rows.
+    # NOTE: the three scaled tags of an lnmf row are one test by construction -- the denominator is constant down a column of W and lnmf.m:70 divides the column by its
+    # sum, so the scale of a row of H_init and whatever the guard puts in its place both cancel; mixed, clamped and p40 return the same W, H and cost to 11 digits.
+    # They certify the range (H at 2^-59 and 2^+40, V ./ V_hat at 2^+-60), not the guard: no case can fail on a change of that guard
+    ("lnmf_96x130x7", "kl"): (-58, -59),
+    ("lnmf_129x131x32", "kl"): (-58, -59),
+    ("constrainednmf_96x130x7", "euclidean"): (-29, -30),
+    ("constrainednmf_96x130x7", "kl"): (-59, -62),
+    ("constrainednmf_129x131x32", "euclidean"): (-28, -30),
+    ("constrainednmf_129x131x32", "kl"): (-57, -60),
+    # nmfsc / cnmfsc: the guard of the row's multiplicative step in the first iteration (the call re-normalises after it).  Integers where one qualifies, else halves, else
+    # eighths: the denominators of one step are sums of like terms and cross eps within a fraction of a binade.  cnmfsc W rows: of the first slice's denominators
+    ("nmfsc_96x130x7_sW0_sH0", "euclidean"): (-29, -30),
+    ("nmfsc_96x130x7_sW0.4_sH0", "euclidean"): (-53, -54),
+    ("nmfsc_96x130x7_sW0_sH0.5", "euclidean"): (-52, -54),
+    ("cnmfsc_96x130x7x3_sW0_sH0", "euclidean"): (-30.75, -31),
+    ("cnmfsc_132x131x32x3_sW0_sH0", "euclidean"): (-32.125, -32.5),
+    ("cnmfsc_96x130x7x3_sW0_sH0.5", "euclidean"): (-53.5, -54.5),
+    ("cnmfsc_132x131x32x3_sW0_sH0.5", "euclidean"): (-55.75, -56.5),
+    # cmfwisa: (mixed, clamped) of the W-step guard max(D, eps), then of the H-step guard max(D + lambda, eps).  The H-step guard is clamped from p = -56 on, where
+    # the fp32 numerator A_i * H_i' falls to 2^-111, inside the 2^20 margin the host file keeps above fp32's smallest normal number: no `hclamped` case (None).  Another shape does not
+    # help: A_i * H_i' is a sum over the n columns of terms at 2^(2p), whatever K_i is, so staying above 2^-106 at p = -56 takes n near 2^11, no small case
+    ("cmfwisa_64x96_5+8", "euclidean"): (-30, -31, -54, None),
+    ("cmfwisa_64x96_2+3+2+4+3", "euclidean"): (-30, -31, -55, None),
+    ("cmfwisa_65x130_5+3", "euclidean"): (-30, -31, -55, None),
+    # wnmf_batch: the zero weights thin the W-step sums out, so the guard is reached two to four binades earlier than in the nmf_batch row
+    ("wnmfbatch_70x5_mask", "euclidean"): (-25, -31),
+    ("wnmfbatch_70x5_mask", "kl"): (-53, -63),
+    ("wnmfbatch_70x5_weights", "euclidean"): (-25, -31),
+    ("wnmfbatch_70x5_weights", "kl"): (-52, -63),
 }
 
 
@@ -180,12 +355,49 @@ SCALED_P = {
 IS_HGUARD_P = 57
 
 
+# wnmf_batch is float64 throughout (only V and the weights are fp32 values), so the euclidean H-step denominator W' * (M .* V_hat) can be taken below eps with nothing
+# leaving a number format: the largest p at which the H-step guard of nb_pass.h replaces 10-90 % of the denominators (pooled over the batch) in some iteration, without lambda
+# (`hmixed`) and with lambda = 2^-54 (`hsparse`: pos + lambda < eps) alike
+BATCH_HGUARD_P = {("wnmfbatch_70x5_mask", "euclidean"): -52, ("wnmfbatch_70x5_weights", "euclidean"): -52}
+
+
+# `sens` per key: the largest movement of the float64 reference, over the cases of the key, when W_init and H_init are rounded to fp32 once -- (on W, H and the further
+# outputs; on the cost).  nmfsc, cnmfsc and cmfwisa allow max(contract, 2 * sens) in their own files; every figure here is below a twentieth of the contract, so the
+# contract alone is the bar of these rows.  Computed and pinned by tests/test_regime_inputs_host.py::test_reference_sensitivity (within a factor 2)
+SENS = {
+    "nmfsc_96x130x7_sW0_sH0": (2.0e-8, 3.6e-9),
+    "nmfsc_96x130x7_sW0.4_sH0": (5.6e-8, 1.4e-9),
+    "nmfsc_96x130x7_sW0_sH0.5": (7.7e-8, 1.6e-9),
+    "cnmfsc_96x130x7x3_sW0_sH0": (2.4e-8, 2.8e-9),
+    "cnmfsc_132x131x32x3_sW0_sH0": (2.7e-8, 7.5e-10),
+    "cnmfsc_96x130x7x3_sW0_sH0.5": (8.1e-8, 3.1e-9),
+    "cnmfsc_132x131x32x3_sW0_sH0.5": (8.1e-8, 6.6e-10),
+    "cmfwisa_64x96_5+8": (4.8e-8, 3.2e-9),
+    "cmfwisa_64x96_2+3+2+4+3": (1.5e-7, 4.0e-8),
+    "cmfwisa_65x130_5+3": (4.7e-8, 3.2e-9),
+}
+
+
 def scaled_tags(row, div):
     """the scaled cases of (row, div): tag -> (p, lambda)"""
+    call = ROWS[row]["call"]
+    if call == "cmfwisa":      # a pair of exponents per guard; lambda (H_sparsity) sits in the H-step guard, so `sparse` runs at the H-step mixed exponent
+        mixed, clamped, hmixed, hclamped = SCALED_P[(key(row), div)]
+        tags = {"mixed": (mixed, 0.0), "clamped": (clamped, 0.0), "hmixed": (hmixed, 0.0), "hclamped": (hclamped, 0.0), "p40": (40, 0.0), "sparse": (hmixed, LAMBDA)}
+        return {t: v for t, v in tags.items() if v[0] is not None}
+    if call in ("lnmf", "nmfsc", "cnmfsc"):      # no lambda in these calls
+        mixed, clamped = SCALED_P[(key(row), div)]
+        tags = {"mixed": (mixed, 0.0), "clamped": (clamped, 0.0), "p40": (40, 0.0)}
+        if ROWS[row].get("sc", (0, 0))[1] > 0:      # W_init * 2^40 under a sparse H: the gradient of the H line search is at 2^80, its first steps overflow to NaN
+            del tags["p40"]                          # and the loop of projfunc.m:27-54 never ends on a NaN (all(v >= 0) stays false) -- the reference has no result there
+        return tags
     if div == "is":
         return {"m40": (-40, 0.0), "p40": (40, 0.0), "hguard": (IS_HGUARD_P, 0.0), "hsparse": (IS_HGUARD_P, LAMBDA)}
     mixed, clamped = SCALED_P[(key(row), div)]
-    return {"mixed": (mixed, 0.0), "clamped": (clamped, 0.0), "p40": (40, 0.0), "sparse": (mixed, LAMBDA)}
+    tags = {"mixed": (mixed, 0.0), "clamped": (clamped, 0.0), "p40": (40, 0.0), "sparse": (mixed, LAMBDA)}
+    if (key(row), div) in BATCH_HGUARD_P:
+        tags.update(hmixed=(BATCH_HGUARD_P[(key(row), div)], 0.0), hsparse=(BATCH_HGUARD_P[(key(row), div)], LAMBDA))
+    return tags
 
 
 # ---- tilted: how much more sensitive the reference itself is per row on tilted data ---------------------------------------------------------------------
@@ -230,15 +442,31 @@ TILT_RATIO = {
     ("cnmf_129x333x64x2", "is"): (12.4, 3.73),
     ("nmfbatch_70x5", "euclidean"): (9.02, 1.94),
     ("nmfbatch_70x5", "kl"): (17.9, 1.85),
+    ("lnmf_96x130x7", "kl"): (1.14, 6.04),
+    ("lnmf_129x131x32", "kl"): (1.24, 5.24),
+    ("constrainednmf_96x130x7", "euclidean"): (11.4, 1.65),
+    ("constrainednmf_96x130x7", "kl"): (21.1, 1.39),
+    ("constrainednmf_96x130x7", "is"): (19.9, 1.3),
+    ("constrainednmf_129x131x32", "euclidean"): (5.21, 1.51),
+    ("constrainednmf_129x131x32", "kl"): (22.3, 1.62),
+    ("constrainednmf_129x131x32", "is"): (9.56, 3.24),
+    ("cmfwisa_64x96_5+8", "euclidean"): (1.14, 1.0),
+    ("cmfwisa_64x96_2+3+2+4+3", "euclidean"): (1.07, 1.14),
+    ("cmfwisa_65x130_5+3", "euclidean"): (1.56, 1.18),
 }
 
 
 def problems(row, family, div, tag=""):
     """the problems of a case: a list of (V, W_init, H_init), and the sparsity lambda of the case"""
     lam, out = 0.0, []
+    addon = ROWS[row]["call"] in ADDON_CALLS
     for b, (m, n, K, T) in enumerate(shapes(row, family)):
+        p = 0
         if family == "scaled":
             p, lam = scaled_tags(row, div)[tag]
+        if addon:
+            out.append(addon_problem(row, family, p, tag, m, n, K, T, b))
+        elif family == "scaled":
             out.append(scaled(m, n, K, T, p=p, b=b))
         elif family == "tilted":
             out.append(tilted(m, n, K, T, decades=0 if tag == "flat" else 12, b=b))
@@ -256,7 +484,7 @@ def cases():
     out = []
     for row in SCALED_ROWS:
         for div in ROWS[row]["divs"]:
-            out += [(row, "scaled", div, tag) for tag in (("m40", "p40", "hguard", "hsparse") if div == "is" else ("mixed", "clamped", "p40", "sparse"))]
+            out += [(row, "scaled", div, tag) for tag in scaled_tags(row, div)]
     for row in OTHER_ROWS:
         for div in ROWS[row]["divs"]:
             out += [(row, "tilted", div, ""), (row, "zeros_wh", div, "")]
@@ -264,6 +492,13 @@ def cases():
         for div in ROWS[row]["divs"]:
             out.append((row, "zeros_v", div, ""))
         out.append((row, "zeros_v", "euclidean", "rowcol"))
+    for row in ADDON_ROWS:
+        for div in ROWS[row]["divs"]:
+            out += [(row, "zeros_wh", div, ""), (row, "zeros_v", div, "")]
+            if row in ADDON_TILTED_ROWS:
+                out.append((row, "tilted", div, ""))
+        if row in ADDON_ROWCOL_ROWS:
+            out.append((row, "zeros_v", "euclidean", "rowcol"))
     return out
 
 

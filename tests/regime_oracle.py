@@ -18,6 +18,9 @@ def run_one(row, M, prob, div, lam, trace=None):
     """the reference of one problem of a row: nmf_oracle for nmf / cnmf and the batch calls (every problem alone), the weighted statements for wnmf / wcnmf"""
     from oracle import nmf_oracle as O
     call = R.ROWS[row]["call"]
+    if call in R.ADDON_CALLS and call != "wnmf_batch":
+        assert trace is None
+        return run_addon(row, prob, div, lam)
     V, W0, H0 = prob
     K = H0.shape[0]
     cfg = _cfg(div, W0, H0, lam)
@@ -32,7 +35,7 @@ def run_one(row, M, prob, div, lam, trace=None):
             w = wcnmf(V, np.ones_like(V), K, T, cfg, trace=trace)
             assert np.allclose(w[0], out[0], rtol=1e-9, atol=0, equal_nan=True) and np.allclose(w[1], out[1], rtol=1e-9, atol=0, equal_nan=True)
         return out
-    if call == "wnmf":
+    if call in ("wnmf", "wnmf_batch"):
         from wnmf_oracle import wnmf
         return wnmf(V, M, K, cfg, trace=trace)
     from wcnmf_oracle import wcnmf
@@ -49,20 +52,26 @@ def _freeze(res):
 @functools.lru_cache(maxsize=None)
 def _reference(key, row, family, div, tag):
     probs, lam = R.problems(row, family, div, tag)
-    M = R.weights(row)
+    Ms = weights_per_problem(row, family, len(probs))
     with np.errstate(all="ignore"):
-        return [_freeze(run_one(row, M, p, div, lam)) for p in probs]
+        return [_freeze(run_one(row, M, p, div, lam)) for M, p in zip(Ms, probs)]
+
+
+def weights_per_problem(row, family, count):
+    """the weights of every problem of a case: one matrix for all of them (None: unweighted), or wnmf_batch's own per problem"""
+    M = R.weights(row, family)
+    return M if isinstance(M, list) else [M] * count
 
 
 def reference(row, family, div, tag=""):
-    """[(W, H, cost) per problem] of a case; rows that differ in the path alone share one run"""
+    """[(W, H, cost) per problem] of a case (an add-on call: its further outputs behind them, regime_inputs.EXTRAS); rows that differ in the path alone share one run"""
     first = next(r for r in R.ROWS if R.key(r) == R.key(row))
     return _reference(R.key(row), first, family, div, tag)
 
 
 # ---- what the oracle formed on the way (host file only) ------------------------------------------------------------------------------------------------
 def _normalised_init(call, W0, H0):
-    if call in ("nmf", "nmf_batch", "wnmf"):                          # nmf.m:130-134
+    if call in ("nmf", "nmf_batch", "wnmf", "wnmf_batch"):            # nmf.m:130-134
         return W0 * (1.0 / np.sqrt(np.sum(W0 ** 2, axis=0)))[None, :], H0
     T = W0.shape[2]                                                   # cnmf.m:157-166
     w = np.sqrt(np.sum(W0 ** 2, axis=(0, 2))) / T
@@ -74,6 +83,9 @@ def iterations(row, M, prob, div, lam):
     denominators the max(pos + lambda, eps) guard replaces, the fraction of the W-step denominators where pos < eps <= pos + lambda, and name -> (smallest non-zero, largest) magnitude (cost_residual: largest, largest) of every intermediate: V, V_hat, the element maps, the
     numerators and denominators of both steps, the update quotients and the per-element cost terms with their total"""
     call = R.ROWS[row]["call"]
+    if call in R.ADDON_CALLS and call != "wnmf_batch":
+        with np.errstate(all="ignore"):
+            return ADDON_ITERATIONS[call](row, prob, div, lam)
     V, W0, H0 = prob
     M = np.ones_like(V) if M is None else M
     on = M > 0
@@ -140,11 +152,9 @@ def iterations(row, M, prob, div, lam):
 def row_movement(row, M, prob, div):
     """the reference's own conditioning per row: the largest relative movement of a row of its W (all components and time slices of that row) and of a
     column of its H when W_init and H_init are rounded to fp32 once"""
-    V, W0, H0 = prob
-    f32 = lambda x: x.astype(np.float32).astype(np.float64)
     with np.errstate(all="ignore"):
-        W, H, _ = run_one(row, M, prob, div, 0.0)
-        W2, H2, _ = run_one(row, M, (V, f32(W0), f32(H0)), div, 0.0)
+        W, H = run_one(row, M, prob, div, 0.0)[:2]
+        W2, H2 = run_one(row, M, rounded_inits(prob), div, 0.0)[:2]
     return per_row(W2, W), per_col(H2, H)
 
 
@@ -169,3 +179,305 @@ def tilt_ratio(row, div):
         probs, _ = R.problems(row, "tilted", div, tag)
         mv[tag] = np.max([row_movement(row, M, p, div) for p in probs], axis=0)
     return max(1.0, mv[""][0] / mv["flat"][0]), max(1.0, mv[""][1] / mv["flat"][1])
+
+
+# ---- the add-on calls (regime_inputs.ADDON_CALLS): their references and what these form on the way ---------------------------------------------------
+def rounded_inits(prob):
+    """the problem with W_init and H_init (lists: every source's) rounded to fp32 once: what the sensitivity figures move the reference by"""
+    V, W0, H0 = prob
+    f32 = lambda x: [f32(a) for a in x] if isinstance(x, list) else x.astype(np.float32).astype(np.float64)
+    return V, f32(W0), f32(H0)
+
+
+def addon_config(row, div, prob, lam):
+    """the configuration of an add-on call on a problem, as the oracle and the library both take it (the library adds the row's cfg)"""
+    r = R.ROWS[row]
+    call = r["call"]
+    V, W0, H0 = prob
+    cfg = dict(W_init=W0, maxiter=R.ITERS, tolerance=R.NO_STOP)
+    if call == "constrainednmf":
+        cfg.update(Z_init=H0, divergence=div)
+        if lam:
+            cfg.update(W_sparsity=lam, Z_sparsity=lam)
+        return cfg
+    cfg["H_init"] = H0
+    if call in ("nmfsc", "cnmfsc"):
+        cfg.update({k: v for k, v in zip(("W_sparsity", "H_sparsity"), r["sc"]) if v > 0})
+    elif call == "cmfwisa":
+        cfg["P_init"] = R.phases(row)
+        if lam:
+            cfg["H_sparsity"] = lam
+    return cfg
+
+
+def run_addon(row, prob, div, lam):
+    """(W, H, cost) and the further outputs regime_inputs.EXTRAS names: constrainednmf Z; cmfwisa P (sources x m x n) and V_hat, its W and H as
+    [W_1 ... W_I] and [H_1; ...; H_I]"""
+    from oracle import nmf_oracle as O
+    r = R.ROWS[row]
+    call = r["call"]
+    V, W0, H0 = prob
+    cfg = addon_config(row, div, prob, lam)
+    if call == "lnmf":
+        return O.lnmf(V, H0.shape[0], cfg)
+    if call == "constrainednmf":
+        W, H, Z, _, c = O.constrainednmf(V, R.labels(row), W0.shape[1], cfg)
+        return W, H, c, Z
+    if call == "nmfsc":
+        return O.nmfsc(V, H0.shape[0], cfg)
+    if call == "cnmfsc":
+        return O.cnmfsc(V, H0.shape[0], W0.shape[2], cfg)
+    import cmfwisa_oracle as CO
+    W, H, P, c = CO.cmfwisa(V, list(r["Ks"]), cfg)
+    P = np.stack(P)
+    return np.hstack(W), np.vstack(H), c, P, sum((w @ h) * q for w, h, q in zip(W, H, P))
+
+
+def flatten_outputs(call, out):
+    """the library's outputs of an add-on call in the layout of run_addon"""
+    if call == "constrainednmf":
+        W, H, Z, _, c = out
+        return W, H, c, Z
+    if call == "cmfwisa":
+        W, H, P, c = out
+        P = np.stack([np.asarray(q, dtype=np.complex128) for q in P])
+        return np.hstack(W), np.vstack(H), c, P, sum((np.asarray(w, dtype=np.float64) @ np.asarray(h, dtype=np.float64)) * q for w, h, q in zip(W, H, P))
+    return out
+
+
+def rel(a, b):
+    """relative Frobenius error, complex arrays included"""
+    a, b = np.asarray(a), np.asarray(b)
+    return float(np.linalg.norm((a - b).ravel()) / max(np.linalg.norm(b.ravel()), 1e-300))
+
+
+def sensitivity(row, family, div, tag=""):
+    """`sens` of a case: how far the float64 reference itself moves (relative Frobenius, per output in the order of run_addon; the worst problem) when
+    W_init and H_init are rounded to fp32 once -- V is an fp32 value already.  cmfwisa is held to max(contract, 2 * sens), as in its own file"""
+    probs, lam = R.problems(row, family, div, tag)
+    refs = reference(row, family, div, tag)
+    out = []
+    with np.errstate(all="ignore"):
+        for prob, ref in zip(probs, refs):
+            got = run_addon(row, rounded_inits(prob), div, lam)
+            out.append([rel(g, r0) if np.all(np.isfinite(r0)) else 0.0 for g, r0 in zip(got, ref)])
+    return tuple(float(x) for x in np.max(np.array(out), axis=0))
+
+
+class _Mags(dict):
+    """name -> (smallest non-zero, largest) magnitude of everything noted under the name"""
+    def note(self, name, x, largest_only=False):
+        a = np.abs(np.asarray(x))
+        a = a[a > 0]
+        if a.size:
+            lo, hi = self.get(name, (np.inf, 0.0))
+            self[name] = (min(lo, float(a.max() if largest_only else a.min())), max(hi, float(a.max())))
+
+
+def _it(mags, pos_w=None, pos_h=None, lam=0.0, lam_in="W"):
+    """one entry of iterations(): the guard fractions of the two denominators given (lambda sits in the one `lam_in` names)"""
+    frac = lambda pos, l: float(np.mean(pos + l < EPS)) if pos is not None else 0.0
+    lw, lh = (lam if lam_in in ("W", "WH") else 0.0), (lam if lam_in in ("H", "WH") else 0.0)
+    pos_l = pos_w if lam_in in ("W", "WH") else pos_h
+    return dict(guard_W=frac(pos_w, lw), guard_H=frac(pos_h, lh), mags=mags,
+                lambda_decides=float(np.mean((pos_l < EPS) & (pos_l + lam >= EPS))) if (lam and pos_l is not None) else 0.0)
+
+
+def _ends_where(got, ref, what):
+    for g, r0 in zip(got, ref):
+        assert np.allclose(g, r0, rtol=1e-9, atol=0, equal_nan=True), what
+
+
+def _lnmf_iterations(row, prob, div, lam):
+    """lnmf.m:59-81 restated with what both steps form kept (oracle/nmf_oracle.py keeps no trace); ends where the oracle ends"""
+    V, W0, H = prob
+    W = W0 * (1.0 / np.sum(W0, axis=0))[None, :]
+    out, cost = [], []
+    for it in range(R.ITERS):
+        mags = _Mags()
+        S = W @ H
+        A, P = V / S, np.ones_like(V) @ H.T
+        N = A @ H.T
+        for nm, x in (("V", V), ("V_hat", S), ("A", A), ("W_num", N), ("W_den", P), ("W_quot", N / np.fmax(P, EPS))):
+            mags.note(nm, x)
+        W = W * (N / np.fmax(P, EPS))
+        mags.note("W_raw", W)
+        mags.note("W_colsum", np.sum(W, axis=0))
+        W = W * (1.0 / np.sum(W, axis=0))[None, :]
+        S = W @ H
+        G = W.T @ (V / S)
+        for nm, x in (("V_hat", S), ("A", V / S), ("H_num", G), ("H_arg", H * G)):
+            mags.note(nm, x)
+        H = np.sqrt(H * G)
+        S = W @ H
+        mags.note("H", H)
+        mags.note("V_hat", S)
+        mags.note("cost_terms", V[V > 0] / S[V > 0])
+        mags.note("cost_residual", V * np.log(V / S) - V + S, largest_only=True)
+        cost.append(np.sum(V * np.log(V / S) - V + S))
+        if np.isfinite(cost[-1]):
+            mags.note("cost", cost[-1])
+        out.append(_it(mags, pos_w=P))
+    _ends_where((W, H, cost), run_addon(row, prob, div, lam), "lnmf restated")
+    return out
+
+
+def _constrainednmf_iterations(row, prob, div, lam):
+    """constrainednmf.m:183-251 restated in the original sample order (A from the oracle: the sort of constrainednmf.m:163 only permutes the columns every sum
+    runs over); ends where the oracle ends"""
+    from oracle import nmf_oracle as O
+    V, W0, Z = prob
+    Am = O.constrainednmf(V, R.labels(row), W0.shape[1], dict(addon_config(row, div, prob, lam), maxiter=1))[3]
+    one, on = np.ones_like(V), np.ones(V.shape, dtype=bool)
+    W = W0 * (1.0 / np.sqrt(np.sum(W0 ** 2, axis=0)))[None, :]
+    H = Z @ Am
+    out, cost = [], []
+    for it in range(R.ITERS):
+        mags = _Mags()
+        S = W @ H
+        A, B, _ = _maps(div, V, one, S, on)
+        N, P = A @ H.T, B @ H.T
+        neg, pos = N + W * np.sum(W * P, axis=0)[None, :], P + W * np.sum(W * N, axis=0)[None, :]
+        for nm, x in (("V", V), ("V_hat", S), ("A", A), ("B", B), ("W_num", N), ("W_den", P), ("W_neg", neg), ("W_pos", pos), ("W_quot", neg / np.fmax(pos + lam, EPS))):
+            mags.note(nm, x)
+        W = W * (neg / np.fmax(pos + lam, EPS))
+        W = W * (1.0 / np.sqrt(np.sum(W ** 2, axis=0)))[None, :]
+        S = W @ H
+        A, B, _ = _maps(div, V, one, S, on)
+        Gn, Gp = W.T @ A @ Am.T, W.T @ B @ Am.T
+        for nm, x in (("V_hat", S), ("A", A), ("B", B), ("Z_num", Gn), ("Z_den", Gp), ("Z_quot", Gn / np.fmax(Gp + lam, EPS))):
+            mags.note(nm, x)
+        Z = Z * (Gn / np.fmax(Gp + lam, EPS))
+        H = Z @ Am
+        S = W @ H
+        d = _maps(div, V, one, S, on)[2]
+        mags.note("Z", Z)
+        mags.note("V_hat", S)
+        nz = V > 0
+        if div == "euclidean":
+            mags.note("cost_terms", V ** 2)
+            mags.note("cost_residual", (V - S) ** 2, largest_only=True)
+        else:
+            mags.note("cost_terms", V[nz] / S[nz])
+            if div == "is":
+                mags.note("cost_terms", S[nz] / V[nz])
+            else:
+                mags.note("cost_residual", V * np.log(V / S), largest_only=True)
+        cost.append(d + lam * (np.sum(np.abs(W)) + np.sum(np.abs(Z))))
+        if np.isfinite(cost[-1]):
+            mags.note("cost", cost[-1])
+        e = _it(mags, pos_w=pos, pos_h=Gp, lam=lam, lam_in="WH")
+        e["lambda_decides"] = float(np.mean((pos < EPS) & (pos + lam >= EPS)))
+        out.append(e)
+    ref = run_addon(row, prob, div, lam)
+    _ends_where((W, H, cost, Z), ref, "constrainednmf restated")
+    return out
+
+
+def _cmfwisa_iterations(row, prob, div, lam):
+    """cmfwisa.m:176-216 restated on the state of tests/cmfwisa_oracle.py::init with what the E pass and both steps form kept; ends where the oracle ends.  The
+    fp32 quantities of the device path: S_i = W_i*H_i (an fp32 MFMA), A_i = |V_bar_i| ./ beta_i (stored as fp32) and the numerators A_i*H_i', W_i'*A_i"""
+    import cmfwisa_oracle as CO
+    V, W0, H0 = prob
+    st = CO.init(V, list(R.ROWS[row]["Ks"]), addon_config(row, div, prob, lam))
+    W, H, P, cfg = st["W"], st["H"], st["P"], st["cfg"]
+    I = len(W)
+    out, cost = [], []
+    for it in range(R.ITERS):
+        mags = _Mags()
+        Si = [W[i] @ H[i] for i in range(I)]
+        S = sum(Si)
+        Vhat = sum(Si[i] * P[i] for i in range(I))
+        beta = [Si[i] / S for i in range(I)]
+        Vbar = [Si[i] * P[i] + beta[i] * (V - Vhat) for i in range(I)]
+        A = [np.abs(Vbar[i]) / beta[i] for i in range(I)]
+        mags.note("V", V)
+        mags.note("S", S)
+        for i in range(I):
+            for nm, x in (("S_i", Si[i]), ("beta", beta[i]), ("V_bar", Vbar[i]), ("A", A[i])):
+                mags.note(nm, x)
+            P[i] = np.exp(1j * np.angle(Vbar[i]))
+        W_all, H_all = np.hstack(W), np.vstack(H)
+        WH = W_all @ H_all
+        dws, dhs = [], []
+        for i in range(I):
+            N, D = A[i] @ H[i].T, WH @ H[i].T
+            dws.append(D.ravel())
+            for nm, x in (("W_num", N), ("W_den", D), ("W_quot", N / np.fmax(D, EPS))):
+                mags.note(nm, x)
+            W[i] = W[i] * (N / np.fmax(D, EPS))
+            W[i] = W[i] * (1.0 / np.sqrt(np.sum(W[i] ** 2, axis=0)))[None, :]
+        for i in range(I):
+            N, D = W[i].T @ A[i], W[i].T @ W_all @ H_all
+            dhs.append(D.ravel())
+            for nm, x in (("H_num", N), ("H_den", D), ("H_quot", N / np.fmax(D + lam, EPS))):
+                mags.note(nm, x)
+            H[i] = H[i] * (N / np.fmax(D + lam, EPS))
+            mags.note("H", H[i])
+        Vhat = sum((W[i] @ H[i]) * P[i] for i in range(I))
+        mags.note("cost_terms", np.abs(V) ** 2)
+        mags.note("cost_residual", np.abs(V - Vhat) ** 2, largest_only=True)
+        cost.append(np.sum(np.abs(V - Vhat) ** 2) + sum(lam * np.sum(h) for h in H))
+        mags.note("cost", cost[-1])
+        out.append(_it(mags, pos_w=np.concatenate(dws), pos_h=np.concatenate(dhs), lam=lam, lam_in="H"))
+    ref = run_addon(row, prob, div, lam)
+    _ends_where((np.hstack(W), np.vstack(H), cost, np.stack(P)), ref[:4], "cmfwisa restated")
+    return out
+
+
+def _sc_first_iteration(row, prob, div, lam):
+    """nmfsc.m:143-232 / cnmfsc.m:157-263: the multiplicative step of the row in the FIRST iteration, restated from the inits -- the call re-normalises after it,
+    so that is where the scaled inits reach the guard.  The H step (H_sparsity = 0) comes first and is formed from the inits alone; the W step (W_sparsity = 0)
+    starts from the H the oracle itself leaves with W_fixed after one iteration (its line search included).  One entry; the magnitudes also cover the
+    oracle's W, H and cost of all iterations"""
+    from oracle import nmf_oracle as O
+    r = R.ROWS[row]
+    V, W0, H0 = prob
+    sW, sH = r["sc"]
+    K = H0.shape[0]
+    T = W0.shape[2] if W0.ndim == 3 else None
+    n = V.shape[1]
+    Vn = V / V.max()
+    W3 = W0.reshape(W0.shape[0], K, -1)
+    rfd = lambda Wx, Hx: O.reconstruct_from_decomposition(Wx[:, :, 0] if Wx.shape[2] == 1 else Wx, Hx)
+    mags = _Mags()
+    cfg = addon_config(row, div, prob, lam)
+    pos_w = pos_h = None
+    if r["guard"] == "H":
+        assert sH == 0
+        Wp = W3.copy()
+        if sW > 0:      # the initial projection (nmfsc.m:87-97; cnmfsc.m:94-112 projects W and keeps W0 for the H step)
+            L1a = np.sqrt(V.shape[0]) - (np.sqrt(V.shape[0]) - 1) * sW
+            for t in range(Wp.shape[2]):
+                for k in range(K):
+                    Wp[:, k, t] = O.projfunc(Wp[:, k, t], L1a, 1.0, True)[0]
+        Wh = W3 if T is not None else Wp
+        S = rfd(Wp, H0)
+        neg = sum(Wh[:, :, t].T @ O._lshift(Vn, t + 1, n) for t in range(Wh.shape[2]))
+        pos_h = sum(Wh[:, :, t].T @ O._lshift(S, t + 1, n) for t in range(Wh.shape[2]))
+        quot = neg / (pos_h + EPS) if T is not None else neg / np.fmax(pos_h, EPS)
+        for nm, x in (("V", Vn), ("V_hat", S), ("H_num", neg), ("H_den", pos_h), ("H_quot", quot), ("H_raw", H0 * quot)):
+            mags.note(nm, x)
+    else:
+        assert sW == 0 and sH > 0
+        call = O.nmfsc if T is None else (lambda V_, K_, c: O.cnmfsc(V_, K_, T, c))
+        H1 = call(V, K, dict(cfg, W_fixed=True, maxiter=1))[1]
+        S = rfd(W3, H1)
+        pws = []
+        for t in range(W3.shape[2]):
+            Hs = O._rshift(H1, t + 1, n)
+            neg, pos = Vn @ Hs.T, S @ Hs.T
+            pws.append(pos.ravel())
+            Wt = W3[:, :, t] * (neg / np.fmax(pos, EPS))
+            for nm, x in (("V", Vn), ("V_hat", S), ("W_num", neg), ("W_den", pos), ("W_quot", neg / np.fmax(pos, EPS)), ("W_raw", Wt)):
+                mags.note(nm, x)
+            S = np.fmax(S + (Wt - W3[:, :, t]) @ Hs, 0.0)
+        pos_w = pws[0]      # the first slice: its update restores V_hat, so the later slices of cnmfsc.m:257-263 meet denominators of ordinary size
+    W, H, c = run_addon(row, prob, div, lam)
+    for nm, x in (("W", W), ("H", H), ("cost", c), ("cost_terms", Vn ** 2)):
+        mags.note(nm, x)
+    return [_it(mags, pos_w=pos_w, pos_h=pos_h)]
+
+
+ADDON_ITERATIONS = {"lnmf": _lnmf_iterations, "constrainednmf": _constrainednmf_iterations, "cmfwisa": _cmfwisa_iterations,
+                    "nmfsc": _sc_first_iteration, "cnmfsc": _sc_first_iteration}

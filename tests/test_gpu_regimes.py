@@ -12,7 +12,12 @@ fp32-representable, and these V are -- a factor 2^p keeps them so --, so the der
 decide, without and with lambda = 2^-54 (the row with m = 64 is the one whose H update runs in the fused kernel's own epilogue).  zeros_wh: a zero of the reference is an exact zero of the result, and nothing is NaN.  zeros_v: W and H
 are finite.  tilted: the largest PER-ROW relative error of W (per column of H) is at most the contract times regime_inputs.TILT_RATIO, the ratio by which
 the reference itself is more sensitive per row on tilted data than on untilted data -- the Frobenius norm is blind to the quiet rows, whose norms are
-1e-11 of the loud ones'."""
+1e-11 of the loud ones'.
+
+The add-on calls with guard copies of their own -- lnmf, constrainednmf, nmfsc, cnmfsc, cmfwisa, wnmf_batch (regime_inputs.ADDON_ROWS) -- run the same families.  What they return besides
+W, H and the cost (constrainednmf: Z; cmfwisa: P and V_hat, its W and H as the sources side by side) is held to the bar of W and H; a zero of Z_init stays an exact zero of Z.
+nmfsc, cnmfsc and cmfwisa keep the plain contract: tests/test_regime_inputs_host.py pins the movement of their references under one fp32 rounding of the inits
+(regime_inputs.SENS), a twentieth of the contract at most.  wnmf_batch keeps the bars of tests/test_gpu_wnmf_batch.py, imported from there: 1e-9, on the cost relative where n_b > K and against the first cost where n_b <= K."""
 import numpy as np
 import pytest
 
@@ -20,6 +25,7 @@ import regime_inputs as R
 import regime_oracle as RO
 import test_gpu_cnmf_batch as TCB
 import test_gpu_nmf64 as T64
+import test_gpu_wnmf_batch as TWB
 from conftest import record_err, rel_fro
 
 pytestmark = pytest.mark.gpu
@@ -27,17 +33,37 @@ pytestmark = pytest.mark.gpu
 max_rel = lambda c, c0: float(np.max(np.abs(c - c0) / np.abs(c0)))
 # row -> (bar on W and H, bar on the cost for euclidean / kl, for is, how the cost error is measured)
 BARS = {"nmf_f64": (T64.TOL_WH, T64.TOL_COST, T64.TOL_COST, max_rel), "nmf_batch": (TCB.TOL, TCB.TOL, TCB.TOL, max_rel),
-        "cnmf_batch": (TCB.TOL, TCB.TOL, TCB.TOL, max_rel)}
+        "cnmf_batch": (TCB.TOL, TCB.TOL, TCB.TOL, max_rel),
+        # wnmf_batch keeps the bars of its own file: 1e-9, on the cost relative where n_b > K and against the first cost where an exact fit exists (n_b <= K)
+        "wnmf_batch_mask": (TWB.TOL, TWB.TOL, TWB.TOL, max_rel), "wnmf_batch_weights": (TWB.TOL, TWB.TOL, TWB.TOL, max_rel)}
+F64_ROWS = ("nmf_f64", "nmf_batch", "cnmf_batch", "wnmf_batch_mask", "wnmf_batch_weights")
+max_abs_first = lambda c, c0: float(np.max(np.abs(c - c0)) / c0[0])
 CONTRACT = (1e-5, 1e-6, 1e-5, rel_fro)
 
 
-def _run(lib, row, probs, div, lam):
+def _run(lib, row, probs, div, lam, family="scaled"):
     """the library call of a row on the problems of a case -> [(W, H, cost) per problem]"""
     r = R.ROWS[row]
     cfg = dict(r["cfg"], divergence=div, maxiter=R.ITERS, tolerance=R.NO_STOP, nmfx_disable_stop=True)
     if lam:
         cfg.update(W_sparsity=lam, H_sparsity=lam)
-    call, K = r["call"], probs[0][2].shape[0]
+    call = r["call"]
+    if call == "wnmf_batch":
+        cfg.update(W_init=[p[1] for p in probs], H_init=[p[2] for p in probs])
+        return list(zip(*lib.wnmf_batch([p[0] for p in probs], R.weights(row, family), probs[0][2].shape[0], cfg)))
+    if call in R.ADDON_CALLS:      # one problem; the outputs in the layout of regime_oracle.run_addon
+        V, W0, H0 = probs[0]
+        cfg = dict(RO.addon_config(row, div, probs[0], lam), nmfx_disable_stop=True, **r["cfg"])
+        if call == "lnmf":
+            return [lib.lnmf(V, H0.shape[0], cfg)]
+        if call == "nmfsc":
+            return [lib.nmfsc(V, H0.shape[0], cfg)]
+        if call == "cnmfsc":
+            return [lib.cnmfsc(V, H0.shape[0], W0.shape[2], cfg)]
+        if call == "constrainednmf":
+            return [RO.flatten_outputs(call, lib.constrainednmf(V, R.labels(row), W0.shape[1], cfg))]
+        return [RO.flatten_outputs(call, lib.cmfwisa(V, list(r["Ks"]), cfg))]
+    K = probs[0][2].shape[0]
     if call in ("nmf_batch", "cnmf_batch"):
         cfg.update(W_init=[p[1] for p in probs], H_init=[p[2] for p in probs])
         Vs = [p[0] for p in probs]
@@ -60,19 +86,28 @@ def test_regime(gpu_lib, case):
     probs, lam = R.problems(row, family, div, tag)
     refs = RO.reference(row, family, div, tag)
     with np.errstate(all="ignore"):
-        gots = _run(gpu_lib, row, probs, div, lam)
+        gots = _run(gpu_lib, row, probs, div, lam, family)
     tol_wh, tol_cost, tol_cost_is, cost_err = BARS.get(row, CONTRACT)
     tol_cost = tol_cost_is if div == "is" else tol_cost
-    sfx = "_f64" if row in ("nmf_f64", "nmf_batch", "cnmf_batch") else ""      # the float64 drivers' figures are kept apart from the fp32 paths'
+    sfx = "_f64" if row in F64_ROWS else ""      # the float64 drivers' figures are kept apart from the fp32 paths'
     rec = lambda **kw: record_err(**{"%s_%s%s" % (family, k, sfx): v for k, v in kw.items()})
     assert len(gots) == len(refs)
     failures = []
-    for b, ((W, H, c), (W0, H0, c0)) in enumerate(zip(gots, refs)):
+    extras = R.EXTRAS.get(R.ROWS[row]["call"], ())
+    for b, (got, ref) in enumerate(zip(gots, refs)):
+        (W, H, c), (W0, H0, c0) = got[:3], ref[:3]
         W, H, c = np.asarray(W, dtype=np.float64), np.asarray(H, dtype=np.float64), np.asarray(c, dtype=np.float64)
-        assert W.shape == W0.shape and H.shape == H0.shape and len(c) == len(c0) == R.ITERS
+        assert W.shape == W0.shape and H.shape == H0.shape and len(c) == len(c0) and len(got) == len(ref) == 3 + len(extras)
+        assert len(c0) == R.ITERS or "sc" in R.ROWS[row]      # nmfsc / cnmfsc: the cost before the first iteration leads, and a line search may end the run (the host file pins the lengths)
         e = rec(W=rel_fro(W, W0), H=rel_fro(H, H0))
+        for name, x, x0 in zip(extras, got[3:], ref[3:]):      # constrainednmf: Z; cmfwisa: P and V_hat -- held to the bar of W and H
+            assert x.shape == x0.shape
+            e.update(rec(**{name: RO.rel(x, x0)}))
         if np.all(np.isfinite(c0)):
-            e.update(rec(cost=cost_err(c, c0) if np.all(np.isfinite(c)) else np.inf))
+            ce = cost_err
+            if R.ROWS[row]["call"] == "wnmf_batch" and probs[b][0].shape[1] <= H0.shape[0]:
+                ce = max_abs_first
+            e.update(rec(cost=ce(c, c0) if np.all(np.isfinite(c)) else np.inf))
         if family == "tilted":
             e.update(rec(W_row=RO.per_row(W, W0), H_col=RO.per_col(H, H0)))
         print(R.case_id(case), b, e)
@@ -80,7 +115,7 @@ def test_regime(gpu_lib, case):
         ok = lambda name, bar: failures.append((b, name, e[name], bar)) if not e[name] <= bar else None
         for name in e:
             kind = name[len(family) + 1:len(name) - len(sfx)]
-            if kind in ("W", "H"):
+            if kind in ("W", "H") + extras:
                 ok(name, tol_wh)
             elif kind == "cost":
                 ok(name, tol_cost)
@@ -89,11 +124,14 @@ def test_regime(gpu_lib, case):
         if not np.all(np.isfinite(c0)):      # the same NaN / +-Inf pattern
             if not (np.array_equal(np.isnan(c), np.isnan(c0)) and np.array_equal(c[~np.isnan(c0)], c0[~np.isnan(c0)])):
                 failures.append((b, "cost pattern", c, c0))
-        if family == "zeros_v" and not (np.all(np.isfinite(W)) and np.all(np.isfinite(H))):
+        if family == "zeros_v" and not (np.all(np.isfinite(W)) and np.all(np.isfinite(H)) and all(np.all(np.isfinite(x)) for x in got[3:])):
             failures.append((b, "non-finite W or H"))
         if family == "zeros_wh":
             if np.isnan(W).any() or np.isnan(H).any() or np.isnan(c).any():
                 failures.append((b, "NaN"))
-            if not (np.array_equal(W == 0, W0 == 0) and np.array_equal(H == 0, H0 == 0)):
+            sW, sH = R.ROWS[row].get("sc", (0, 0))      # nmfsc / cnmfsc: the zero pattern of the multiplicative factor; a projected factor is judged by its error alone
+            if not ((sW > 0 or np.array_equal(W == 0, W0 == 0)) and (sH > 0 or np.array_equal(H == 0, H0 == 0))):
                 failures.append((b, "zeros moved", int(np.sum((W == 0) != (W0 == 0))), int(np.sum((H == 0) != (H0 == 0)))))
+            if "Z" in extras and not (np.array_equal(got[3] == 0, ref[3] == 0) and not np.isnan(got[3]).any()):
+                failures.append((b, "zeros of Z moved"))
     assert not failures, failures

@@ -1,7 +1,9 @@
 """The conditions under which tests/test_gpu_regimes.py means something, checked on the float64 reference alone (no GPU): for every case of
 tests/regime_inputs.py the reference stays finite and its cost has the expected non-finite pattern; the scaled cases reach the max(pos + lambda, eps)
 guard as often as their names say, and everything an fp32 path forms on them is a normal fp32 number with a factor 2^20 to spare; the per-row
-sensitivity ratios of the tilted cases are the constants stored next to the inputs."""
+sensitivity ratios of the tilted cases are the constants stored next to the inputs.  For the add-on calls (regime_inputs.ADDON_ROWS) the steps are restated in
+tests/regime_oracle.py with their denominators kept, and every restatement must end where the oracle ends; FP32_HELD names what the device holds in fp32 where a call keeps the
+rest in float64."""
 import numpy as np
 import pytest
 
@@ -10,6 +12,10 @@ import regime_oracle as RO
 
 SPARE = 2.0 ** 20
 F32_MIN, F32_MAX = 2.0 ** -126, 2.0 ** 127
+# what the device holds in fp32 where a call keeps the rest in float64 (None, the default: everything noted).  cmfwisa: V, S_i = W_i * H_i (an fp32 MFMA on the
+# fp32 images of W and H), A_i = |V_bar_i| ./ beta_i and the numerators A_i * H_i', W_i' * A_i; the denominators, the updates and the cost are float64
+# (csrc/cmfwisa.hip).  wnmf_batch: V and the weights alone (every contraction and every update of csrc/wnmf_batch.hip is float64)
+FP32_HELD = {"cmfwisa": ("V", "S_i", "A", "W_num", "H_num", "H"), "wnmf_batch": ("V",)}
 
 
 def _unique(cases):
@@ -30,9 +36,10 @@ SCALED = [c for c in CASES if c[1] == "scaled"]
 def test_every_row_of_the_table_is_covered():
     rows = {c[0] for c in R.cases() if c[1] == "scaled"}
     assert rows == set(R.ROWS)
-    for fam in ("tilted", "zeros_wh"):
-        assert {c[0] for c in R.cases() if c[1] == fam} == set(R.OTHER_ROWS)
-    assert {c[0] for c in R.cases() if c[1] == "zeros_v"} == set(R.ZEROS_V_ROWS)
+    assert {c[0] for c in R.cases() if c[1] == "tilted"} == set(R.OTHER_ROWS + R.ADDON_TILTED_ROWS)
+    assert {c[0] for c in R.cases() if c[1] == "zeros_wh"} == set(R.OTHER_ROWS + R.ADDON_ROWS)
+    assert {c[0] for c in R.cases() if c[1] == "zeros_v"} == set(R.ZEROS_V_ROWS + R.ADDON_ROWS)
+    assert {R.ROWS[r]["call"] for r in R.ADDON_ROWS} == set(R.ADDON_CALLS)
     assert len(R.cases()) == len(set(R.cases()))
 
 
@@ -42,9 +49,14 @@ def test_reference_is_finite_with_the_expected_cost_pattern(case):
     probs, _ = R.problems(row, family, div, tag)
     refs = RO.reference(row, family, div, tag)
     assert len(refs) == len(probs)
-    for (V, W0, H0), (W, H, c) in zip(probs, refs):
-        assert np.array_equal(V, V.astype(np.float32).astype(np.float64))          # the device's fp32 copy of V is lossless
-        assert np.all(np.isfinite(W)) and np.all(np.isfinite(H)) and len(c) == R.ITERS
+    for (V, W0, H0), ref in zip(probs, refs):
+        W, H, c = ref[:3]
+        assert np.array_equal(V, V.astype(np.complex64 if np.iscomplexobj(V) else np.float32).astype(V.dtype))          # the device's fp32 copy of V is lossless
+        # (nmfsc with a sparse W ends its first W line search by step-size underflow, nmfsc.m:221-225, on every input here: the H of that one step and one cost come back)
+        assert np.all(np.isfinite(W)) and np.all(np.isfinite(H)) and len(c) == (1 if R.ROWS[row].get("sc") == (0.4, 0.0) else R.ITERS + ("sc" in R.ROWS[row]))
+        assert len(ref) == 3 + len(R.EXTRAS.get(R.ROWS[row]["call"], ())) and all(np.all(np.isfinite(x)) for x in ref[3:])      # Z; P and V_hat
+        if isinstance(W0, list):                                                    # cmfwisa: the sources side by side, as the reference returns them
+            W0, H0 = np.hstack(W0), np.vstack(H0)
         if family == "zeros_v" and div == "kl":
             assert np.all(np.isnan(c))                                              # 0 * log(0)
         elif family == "zeros_v" and div == "is":
@@ -60,29 +72,44 @@ def test_reference_is_finite_with_the_expected_cost_pattern(case):
                 assert not z.all(axis=1).any() and not z.all(axis=0).any()
         if family == "zeros_wh":
             zw, zh = W0 == 0, H0 == 0
-            assert 0.25 < zw.mean() < 0.45 and 0.25 < zh.mean() < 0.45
+            lo = 0.25
+            if R.ROWS[row]["call"] == "cmfwisa":      # cmfwisa keeps the first component of EVERY source positive: 0.4 * (1 - I / K_all) expected, 0.257 with five sources of 14
+                Ks = R.ROWS[row]["Ks"]
+                lo = 0.9 * 0.4 * (1 - len(Ks) / sum(Ks))
+            assert lo < zw.mean() < 0.45 and lo < zh.mean() < 0.45
             assert not zw.reshape(zw.shape[0], zw.shape[1], -1).all(axis=(0, 2)).any() and not zh.all(axis=1).any()
-            assert np.array_equal(np.asarray(W).reshape(W0.shape) == 0, zw) and np.array_equal(H == 0, zh)      # a multiplicative update keeps every zero, and makes none
+            Hz = ref[3] if R.ROWS[row]["call"] == "constrainednmf" else H           # constrainednmf: H0 is Z_init, and H = Z * A repeats the columns of Z
+            sW, sH = R.ROWS[row].get("sc", (0, 0))                                  # nmfsc / cnmfsc: a projected factor keeps no zero pattern, the multiplicative one does
+            assert (sW > 0 or np.array_equal(np.asarray(W).reshape(W0.shape) == 0, zw)) and (sH > 0 or np.array_equal(Hz == 0, zh))      # a multiplicative update keeps every zero, and makes none (lnmf: through its square root)
         if family == "tilted":
-            assert V.max() / V[V > 0].min() > 1e12
+            assert np.abs(V).max() / np.abs(V)[V != 0].min() > 1e12
 
 
 def _iterations(case):
     row, family, div, tag = case
     probs, lam = R.problems(row, family, div, tag)
-    return [RO.iterations(row, R.weights(row), p, div, lam) for p in probs], lam
+    return [RO.iterations(row, M, p, div, lam) for M, p in zip(RO.weights_per_problem(row, family, len(probs)), probs)], lam
 
 
-@pytest.mark.parametrize("case", [c for c in SCALED if c[3] in ("mixed", "clamped", "sparse", "hguard", "hsparse")], ids=R.case_id)
+@pytest.mark.parametrize("case", [c for c in SCALED if c[3] in ("mixed", "clamped", "hmixed", "sparse", "hguard", "hsparse")], ids=R.case_id)
 def test_scaled_guard_fractions(case):
     """per iteration, the fraction of the W-step denominators that max(pos + lambda, eps) replaces, recomputed from the reference's traced states"""
     its, lam = _iterations(case)
-    gw = np.array([[i["guard_W"] for i in prob] for prob in its])                # problems x iterations (every problem has the same number of W entries)
+    r = R.ROWS[case[0]]
+    which = "guard_H" if (r["call"] == "cmfwisa" and case[3] in ("hmixed", "sparse")) or r.get("guard") == "H" else "guard_W"      # cmfwisa: lambda sits in the H-step guard
+    if r["call"] == "wnmf_batch" and case[3] in ("hmixed", "hsparse"):           # the H-step copy of the batch pass: the W step is clamped throughout there
+        gh = np.array([[i["guard_H"] for i in prob] for prob in its]).mean(axis=0)
+        print(case, np.round(gh, 3))
+        assert np.any((gh >= 0.10) & (gh <= 0.90)) and lam == (R.LAMBDA if case[3] == "hsparse" else 0.0), gh
+        return
+    gw = np.array([[i[which] for i in prob] for prob in its])                # problems x iterations (every problem has the same number of W entries)
     pooled = gw.mean(axis=0)
     print(case, np.round(pooled, 3))
-    if case[3] == "clamped":
+    if case[3] == "clamped" and r.get("once"):                                   # lnmf re-balances after one step: all of the first iteration's, none later
+        assert gw[:, 0].min() >= 0.99 and (gw.shape[1] == 1 or gw[:, 1:].max() == 0.0), gw      # (nmfsc / cnmfsc: the first iteration alone is restated)
+    elif case[3] == "clamped":
         assert gw.min() >= 0.99, gw
-    elif case[3] == "mixed":
+    elif case[3] in ("mixed", "hmixed"):
         assert np.any((pooled >= 0.10) & (pooled <= 0.90)), pooled
     elif case[3] in ("hguard", "hsparse"):                                       # is at p = +57: the H-step copies of the guard (hsparse: pos + lambda < eps)
         gh = np.array([[i["guard_H"] for i in prob] for prob in its]).mean(axis=0)
@@ -110,10 +137,43 @@ def test_scaled_stays_inside_fp32(case):
     """V, V_hat, the element maps, the numerators, denominators and quotients of both steps, the per-element cost terms (squares included) and the cost:
     normal fp32 numbers with a factor 2^20 to spare on either side"""
     its, _ = _iterations(case)
+    held = FP32_HELD.get(R.ROWS[case[0]]["call"])
     for prob in its:
         for i in prob:
+            assert held is None or set(held) <= set(i["mags"])
             for name, (lo, hi) in i["mags"].items():
+                if held is not None and name not in held:
+                    continue
                 assert lo >= F32_MIN * SPARE and hi <= F32_MAX / SPARE, (case, name, np.log2(lo), np.log2(hi))
+
+
+SENS_ROWS = [next(r for r in R.ADDON_ROWS if R.key(r) == k) for k in R.SENS]
+
+
+def test_every_row_with_a_sensitivity_allowance_has_its_figure():
+    assert set(R.SENS) == {R.key(r) for r in R.ADDON_ROWS if R.ROWS[r]["call"] in ("nmfsc", "cnmfsc", "cmfwisa")}
+
+
+@pytest.mark.parametrize("row", SENS_ROWS)
+def test_reference_sensitivity(row):
+    """regime_inputs.SENS: the reference's own movement under one fp32 rounding of W_init and H_init, the largest over the cases of the row -- pinned within a factor 2,
+    below the 1e-3 past which a case compares nothing, and with 2 * sens a tenth of the contract at most, so that the contract alone is the bar"""
+    sens = np.array([RO.sensitivity(*c) for c in R.cases() if c[0] == row])
+    got = (float(np.delete(sens, 2, axis=1).max()), float(sens[:, 2].max()))
+    want = R.SENS[R.key(row)]
+    print(row, got, want)
+    for g, w in zip(got, want):
+        assert w / 2 <= g <= 1.05 * w, (got, want)
+    assert 2 * want[0] <= 1e-5 / 10 and 2 * want[1] <= 1e-6 / 10
+
+
+def test_recorded_profile_holds_every_case():
+    """profiles/regime_parity_errors.json, the figures README and DESIGN quote: one entry per case of the GPU file, none left from a table that has changed"""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "regime_parity_errors.json")) as f:
+        recorded = set(json.load(f)["tests"])
+    assert recorded == {"tests/test_gpu_regimes.py::test_regime[%s]" % R.case_id(c) for c in R.cases()}
 
 
 def test_scaled_range_that_is_certified():
