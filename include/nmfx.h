@@ -266,6 +266,26 @@ nmfx_status nmfx_cnmf_batch(const nmfx_problem *p, int32_t batch, const int64_t 
  * NMFX_ERR_NOMEM with the byte count.  nmfx_last_call_timing describes the call. */
 nmfx_status nmfx_wnmf_batch(const nmfx_problem *p, const void *M, int32_t batch, const int64_t *col_offsets /* batch + 1, col_offsets[0] = 0, increasing */,
                             nmfx_result *r, int32_t *cost_len /* batch */);
+/* `batch` independent weighted cnmf problems in one call: nmfx_cnmf_batch's layouts and rules with nmfx_wnmf_batch's weights M (m x N, p->dtype,
+ * column-major, >= 0 and finite, beside p->V).  The problems share m, K_total, T and the configuration; problem b has n_b >= max(1, T - 1) columns.  With
+ * S = sum_t W_t*rshift_t(H_b), on = M > 0:
+ *   euclidean  A = on ? M.*V : 0,  B = on ? M.*S : 0;   kl  A = on ? M.*V./S : 0,  B = on ? M : 0;   cost = sum(on ? M.*d(V, S) : 0) + the L1 terms
+ * W step (cnmf.m:187-199): every slice t takes N_t = A*rshift_t(H_b)' and P_t = B*rshift_t(H_b)' of the iteration's start, then the joint norm over (m, T)
+ * divided by T (H is not rescaled).  H step: Gn(k, j) = sum_t sum_i W_t(i, k)*A(i, j + t), Gp the same over B; a column j + t past the problem's last reads
+ * as 0, except that B reads as 1 there for kl (nmfx_wcnmf's rule: with M == 1 it is cnmf.m:220-221's unshifted denominator).  The maps select on M: where
+ * M == 0 the entry contributes exactly 0 and V is never looked at there (NaN, Inf and negative values are carried along).  Result b is what nmfx_wcnmf
+ * computes for problem b alone, in float64; with M == 1 everywhere it is nmfx_cnmf_batch's, with T = 1 nmfx_wnmf_batch's.  A new entry point; no structure
+ * grows, so NMFX_VERSION stays 600.
+ *   p->V, M  m x N;  p->H_init, r->H  K_total x N;  p->W_init, r->W  m x K_total x T x batch;  r->cost  maxiter x batch, column-major;  cost_len  out [batch]
+ * A NULL M, col_offsets that do not start at 0, increase and end at p->n, and n_b < T - 1 are NMFX_ERR_INVALID; num_sources != 1, every divergence but
+ * euclidean and kl, n_gpus > 1, multi_backend != 0 and K_total * T > 256 are NMFX_ERR_UNSUPPORTED; tolerance < 0 disables the stop rule; path is ignored.
+ * Device arithmetic: V and M are kept as fp32, everything else is float64 (v_mfma_f64_16x16x4_f64); no sum that reaches a result uses an atomic, and a
+ * problem's result does not depend on its place in the batch.  Device memory: 8*m*N (V and M) + 8*K*N (H) + 16*m*K*T*batch (W and its pass operand) +
+ * 16*64*KP bytes per (64 rows, 256 columns) of every problem (KP = K*T rounded up to 32, 64, 128 or 256; both divergences keep two slabs) + 16*K*T*N (the
+ * H-step products WC'*A and WC'*B, both divergences) + 8*K*T*batch (the per-slice column sums of W) + 8*maxiter*batch; a failed allocation is
+ * NMFX_ERR_NOMEM with the byte count.  nmfx_last_call_timing describes the call. */
+nmfx_status nmfx_wcnmf_batch(const nmfx_problem *p, const void *M, int32_t batch, const int64_t *col_offsets /* batch + 1, col_offsets[0] = 0, increasing */,
+                             nmfx_result *r, int32_t *cost_len /* batch */);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,

@@ -1,5 +1,5 @@
-// The pass kernel, the decide kernel and the host helpers that nmf_batch.hip, cnmf_batch.hip and wnmf_batch.hip share.  Included once by each of the three
-// translation units; everything lives in an anonymous namespace, so each gets its own instantiations.  The block reduction is dev_reduce.h's and the float64
+// The pass kernel, the decide kernel and the host helpers that nmf_batch.hip, cnmf_batch.hip, wnmf_batch.hip and wcnmf_batch.hip share (DESIGN 4.10, 4.11, 4.14,
+// 4.15).  Included once by each of the four translation units; everything lives in an anonymous namespace, so each gets its own instantiations.  The block reduction is dev_reduce.h's and the float64
 // staging (ingest64 / egress64) api_common.h's, as in the other add-on drivers; grid_of (a workgroup per item) is this pair's own.
 #pragma once
 #include "api_common.h"
@@ -43,7 +43,7 @@ struct NbPass {
     double *slab;           // W step out: [item][which][k][64 rows]
     double *costpart;       // W step out: [item]
     const double *cw;       // H step, KL: colsum(W_b) [b][k]
-    double *Pbuf;           // H step, euclidean at the widest K: W_b'*S of the first of its two launches, K x N
+    double *Pbuf;           // H step, two accumulator sets at the widest K: W_b'*S (WGT: W_b'*B) of the first of its two launches, K x N
     double lamH;
     const float *M;         // WGT: the weights, m x N beside V
 };
@@ -60,6 +60,9 @@ struct NbPass {
 // where M == 0.  Euclidean: A = on ? M*V : 0 and the second operand on ? M*S : 0.  KL: A = on ? M*V/S : 0 and a second operand on ? M : 0 where the unweighted
 // step has none, so KL carries both accumulator sets, takes the WHICH = 1 / 2 split and the doubled slab like the euclidean step, and its H-step epilogue
 // reads its denominators from the second accumulator (Pbuf) instead of colsum(W); its denominators-only launch (WHICH = 1) forms no S at all.
+//
+// CONV and WGT together (wcnmf_batch.hip): the window operands of CONV under the element maps of WGT.  The H step stores both accumulators,
+// WC'*A to Qbuf and WC'*B to Pbuf (K*T x N each, for kl too), whichever launch holds them.
 template <int KP, int DIV, bool HS, int WHICH, bool CONV, bool WGT = false>
 __global__ __launch_bounds__(256) void nb_pass(const NbPass g) {
     constexpr int LDY = KP + 4, NKB = KP / 16, NKK = KP / 4;
@@ -67,7 +70,6 @@ __global__ __launch_bounds__(256) void nb_pass(const NbPass g) {
     constexpr bool DO_N = WHICH != 1, DO_P = (DIV == NB_EUC || WGT) && WHICH != 2, COST = !HS && DO_N;
     constexpr bool NEED_S = (DIV == NB_KL && DO_N) || (DIV == NB_EUC && DO_P) || COST;
     static_assert(DIV == NB_EUC || WHICH == 0 || WGT, "KL has one contraction");
-    static_assert(!(WGT && CONV), "the convolutive passes have no weights");
     extern __shared__ __align__(16) double Ys[];   // [TS][LDY]
     __shared__ double sh[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;

@@ -16,6 +16,7 @@
     W, H, cost = wnmf(V, M, num_basis_elems, config)              nmf.m:1 with per-entry weights M >= 0 (missing or unreliable data)
     W, H, cost = wcnmf(V, M, num_basis_elems, context_len, config)   cnmf.m:1 with per-entry weights M >= 0
     W, H, cost = wnmf_batch(Vs, Ms, num_basis_elems, config)      wnmf per problem (lists: B independent weighted problems in one call)
+    W, H, cost = wcnmf_batch(Vs, Ms, num_basis_elems, context_len, config)   wcnmf per problem (lists: B independent weighted problems in one call)
 
 Same argument meaning, defaults and error behaviour as the MATLAB functions (a MATLAB cell array is
 a Python list, a struct a dict; errors are ValueError carrying the reference's message).  This file
@@ -281,7 +282,7 @@ def _weighted_inputs(fn, V, M, config):
 
 
 def _weights(fn, M, shape, dtype, name="M", of="V"):
-    """The weight rules of wnmf, wcnmf and wnmf_batch: `name` has the shape of `of`, is of a real kind and every weight is >= 0 and finite, also in
+    """The weight rules of wnmf, wcnmf, wnmf_batch and wcnmf_batch: `name` has the shape of `of`, is of a real kind and every weight is >= 0 and finite, also in
     the dtype it travels in.  Returns it in that dtype, column-major."""
     M = np.asarray(M)
     if M.shape != shape:
@@ -736,6 +737,138 @@ def cnmf_batch(Vs, num_basis_elems, context_len, config=None, device=0):
     r = _lib.Result()
     r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
     _lib.check(_lib.load().nmfx_cnmf_batch(C.byref(p), B, _fptr(off), C.byref(r), _fptr(lens)))
+    return ([np.array(Wout[:, :, 0, b] if T == 1 else Wout[:, :, :, b]) for b in range(B)], [np.array(Hout[:, off[b]:off[b + 1]]) for b in range(B)],
+            [cost[: lens[b], b].copy() for b in range(B)])
+
+
+def wcnmf_batch(Vs, Ms, num_basis_elems, context_len, config=None, device=0):
+    """W, H, cost = wcnmf_batch(Vs, Ms, num_basis_elems, context_len, config): B independent weighted cnmf problems in one call -- three lists of length B,
+    entry b being what wcnmf(Vs[b], Ms[b], num_basis_elems, context_len, config_b) computes: W[b] m-by-K-by-T (m-by-K when T == 1), H[b] K-by-n_b, cost[b]
+    trimmed by that problem's own stop rule.  Every contraction runs in float64 on the device.
+
+    Ms is a list of B weight matrices, Ms[b] of the shape of Vs[b]; the weight rules are wnmf_batch's (bool, integer or float; a negative or non-finite
+    weight is a ValueError) and so is the meaning: where Ms[b] == 0 the entry contributes exactly nothing and Vs[b] is never looked at there -- it may be
+    NaN, Inf or negative.  The updates are wcnmf's, its kl H-step denominator included (the weights read as 1 past a problem's last column).  With
+    Ms[b] == 1 everywhere problem b is cnmf_batch's, with context_len == 1 it is wnmf_batch's.  Everything else is cnmf_batch's: the problems share the
+    number of rows, num_basis_elems (one positive integer: one source), context_len (num_basis_elems * context_len <= 256) and the configuration; every
+    Vs[b] has its own number of columns n_b >= max(1, T - 1); float32 data stays float32 when every Vs[b] is float32, anything else travels as float64, and
+    the weights travel in that dtype; config takes cnmf's keys with cnmf's defaults and clamping, each ONE value for the whole batch: divergence
+    ('euclidean', 'kl' / 'kl_divergence'), W_sparsity, H_sparsity, W_fixed, H_fixed, maxiter, tolerance, nmfx_disable_stop, seed / rng.  H_init is absent
+    (empty) or a list of B matrices K-by-n_b; W_init is absent (empty), ONE m-by-K-by-T tensor used for every problem (with W_fixed: one trained
+    dictionary over a test set, every utterance with its own mask; m-by-K accepted when T == 1) or a list of B of them.  Missing inits are drawn from the
+    one rng problem by problem, in cnmf_batch's order and form.
+
+    Refused with ValueError: everything cnmf_batch refuses (the 'is' / 'ab' divergences, n_b < T - 1 and K * T > 256 included), Ms that is not a list of B
+    arrays, a Ms[b] of another shape than Vs[b] or of a non-real kind, and a weight that is negative or not finite.  nmfx_path is ignored (there is one
+    path)."""
+    cfg = dict(config) if config else {}
+    try:
+        _precision(cfg, "wcnmf_batch")
+    except ValueError as e:
+        raise ValueError(str(e) if "wcnmf_batch" in str(e) else "wcnmf_batch: %s" % e) from None
+    if cfg.get("nmfx_gpus", None) is not None or cfg.get("nmfx_multi_backend", None) is not None:
+        raise ValueError("wcnmf_batch runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported")
+    if not _is_cell(Vs) or len(Vs) == 0:
+        raise ValueError("wcnmf_batch: Vs must be a non-empty list of matrices")
+    Vs = [np.asarray(v) for v in Vs]
+    B = len(Vs)
+    for b, v in enumerate(Vs):
+        if v.ndim != 2:
+            raise ValueError("wcnmf_batch: Vs[%d] must be a matrix" % b)
+        if v.shape[0] != Vs[0].shape[0]:
+            raise ValueError("wcnmf_batch: Vs[%d] has %d rows, Vs[0] has %d: the problems of a batch share their rows" % (b, v.shape[0], Vs[0].shape[0]))
+        if v.shape[1] < 1 or v.shape[0] < 1:
+            raise ValueError("wcnmf_batch: Vs[%d] is empty" % b)
+    if not _is_cell(Ms) or len(Ms) != B:
+        raise ValueError("wcnmf_batch: Ms must be a list of %d weight matrices, one per problem" % B)
+    if _is_cell(num_basis_elems) or np.ndim(num_basis_elems) != 0:
+        raise ValueError("wcnmf_batch: num_basis_elems must be one positive integer (the batch has one source)")
+    K = int(num_basis_elems)
+    if K != num_basis_elems or K <= 0:
+        raise ValueError("wcnmf_batch: num_basis_elems must be a positive integer")
+    if _is_cell(context_len) or np.ndim(context_len) != 0 or isinstance(context_len, bool) or int(context_len) != context_len or int(context_len) <= 0:
+        raise ValueError("wcnmf_batch: context_len must be a positive integer")
+    T = int(context_len)
+    m = Vs[0].shape[0]
+    ns = [v.shape[1] for v in Vs]
+    for b, n in enumerate(ns):
+        if n < T - 1:      # cnmf.m:188: [zeros(K, t-1) H(:, 1:n-t+1)] has the wrong width there and MATLAB errors
+            raise ValueError("wcnmf_batch: Vs[%d] has n_b = %d columns, fewer than T - 1 with T = %d: cnmf.m:188 has no H_shifted there" % (b, n, T))
+    if K * T > 256:
+        raise ValueError("wcnmf_batch: num_basis_elems * context_len = %d, at most 256 is supported" % (K * T))
+    div = cfg.get("divergence", "euclidean")                       # cnmf.m:283-285
+    if not isinstance(div, str) or div not in _DIV_BATCH:
+        raise ValueError("wcnmf_batch has the euclidean and kl divergences only; got %r" % (div,))
+    dt = np.float32 if all(v.dtype == np.float32 for v in Vs) else np.float64
+    Ms = [_weights("wcnmf_batch", M, Vs[b].shape, dt, "Ms[%d]" % b, "Vs[%d]" % b) for b, M in enumerate(Ms)]
+    Hi, Wi = cfg.get("H_init", None), cfg.get("W_init", None)
+    if not _isempty(Hi):
+        if not _is_cell(Hi) or len(Hi) != B:
+            raise ValueError("wcnmf_batch: H_init must be a list of %d matrices" % B)
+        Hi = [np.asarray(h) for h in Hi]
+        for b, h in enumerate(Hi):
+            if h.shape != (K, ns[b]):
+                raise ValueError("wcnmf_batch: H_init[%d] must be %d-by-%d" % (b, K, ns[b]))
+    else:
+        Hi = None
+    if not _isempty(Wi):
+        if _is_cell(Wi):
+            if len(Wi) != B:
+                raise ValueError("wcnmf_batch: W_init must be one %d-by-%d-by-%d tensor or a list of %d of them" % (m, K, T, B))
+            Wi = [np.asarray(w) for w in Wi]
+        else:
+            Wi = [np.asarray(Wi)] * B
+        for b, w in enumerate(Wi):
+            if w.shape != (m, K, T) and not (T == 1 and w.shape == (m, K)):
+                raise ValueError("wcnmf_batch: W_init%s must be %d-by-%d-by-%d" % ("[%d]" % b if _is_cell(cfg["W_init"]) else "", m, K, T))
+    else:
+        Wi = None
+    nonneg = lambda x: max(float(x), 0.0)
+    lw = _per_source(cfg, "W_sparsity", 1, 0.0, nonneg, "sparsity levels")      # cnmf.m:347-436, one source
+    lh = _per_source(cfg, "H_sparsity", 1, 0.0, nonneg, "sparsity levels")
+    fw = _per_source(cfg, "W_fixed", 1, False, bool, "update switches")
+    fh = _per_source(cfg, "H_fixed", 1, False, bool, "update switches")
+    maxiter = cfg.get("maxiter", None)
+    maxiter = 100 if maxiter is None or maxiter <= 0 else int(maxiter)          # cnmf.m:439-441
+    tol = cfg.get("tolerance", None)
+    tol = 1e-3 if tol is None or tol <= 0 else float(tol)                       # cnmf.m:444-446
+    rng = _rng(cfg)
+    off = np.zeros(B + 1, dtype=np.int64)
+    off[1:] = np.cumsum(ns)
+    N = int(off[B])
+    V_all = np.empty((m, N), order="F", dtype=dt)
+    M_all = np.empty((m, N), order="F", dtype=dt)
+    H_all = np.empty((K, N), order="F", dtype=dt)
+    W_all = np.empty((m, K, T, B), order="F", dtype=dt)
+    for b in range(B):
+        lo, hi = off[b], off[b + 1]
+        with np.errstate(invalid="ignore", over="ignore"):      # (what lies under a zero weight is carried along, never looked at)
+            V_all[:, lo:hi] = Vs[b]
+        M_all[:, lo:hi] = Ms[b]
+        H_all[:, lo:hi] = Hi[b] if Hi is not None else np.fmax(rng.rand(K, ns[b]), EPS)     # cnmf.m:312
+        if Wi is not None:
+            W_all[:, :, :, b] = Wi[b].reshape(m, K, T)
+        else:                                                                              # cnmf.m:331-335
+            w = rng.rand(m, K, T)
+            W_all[:, :, :, b] = w / (np.sqrt(np.sum(w ** 2, axis=(0, 2))) / T)[None, :, None]
+    Wout = np.zeros((m, K, T, B), order="F", dtype=dt)
+    Hout = np.zeros((K, N), order="F", dtype=dt)
+    cost = np.zeros((maxiter, B), order="F")
+    lens = np.zeros(B, dtype=np.int32)
+    lw, lh = np.asarray(lw, dtype=np.float64), np.asarray(lh, dtype=np.float64)
+    fw, fh = np.asarray(fw, dtype=np.uint8), np.asarray(fh, dtype=np.uint8)
+    p = _lib.Problem()
+    p.m, p.n, p.K_total, p.T, p.dtype = m, N, K, T, (_lib.F32 if dt == np.float32 else _lib.F64)
+    p.V, p.W_init, p.H_init = _fptr(V_all), _fptr(W_all), _fptr(H_all)
+    p.divergence, p.alpha, p.beta = _DIV_BATCH[div], 1.0, 1.0
+    p.num_sources, p.K_s = 1, None
+    p.W_sparsity, p.H_sparsity, p.W_fixed, p.H_fixed = _fptr(lw), _fptr(lh), _fptr(fw), _fptr(fh)
+    p.maxiter = maxiter
+    p.tolerance = -1.0 if cfg.get("nmfx_disable_stop", False) else tol
+    p.device = int(device)
+    r = _lib.Result()
+    r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
+    _lib.check(_lib.load().nmfx_wcnmf_batch(C.byref(p), _fptr(M_all), B, _fptr(off), C.byref(r), _fptr(lens)))
     return ([np.array(Wout[:, :, 0, b] if T == 1 else Wout[:, :, :, b]) for b in range(B)], [np.array(Hout[:, off[b]:off[b + 1]]) for b in range(B)],
             [cost[: lens[b], b].copy() for b in range(B)])
 
