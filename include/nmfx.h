@@ -286,6 +286,21 @@ nmfx_status nmfx_wnmf_batch(const nmfx_problem *p, const void *M, int32_t batch,
  * NMFX_ERR_NOMEM with the byte count.  nmfx_last_call_timing describes the call. */
 nmfx_status nmfx_wcnmf_batch(const nmfx_problem *p, const void *M, int32_t batch, const int64_t *col_offsets /* batch + 1, col_offsets[0] = 0, increasing */,
                              nmfx_result *r, int32_t *cost_len /* batch */);
+/* Per-source Wiener-style masks from a decomposition, applied to X in the same pass (no reference .m: the definition is this comment and DESIGN 4.16).
+ * Source i owns K_s[i] components; W (m x K x T, K = sum(K_s), the sources side by side along K) and H (K x n) are laid out as nmfx_reconstruct takes them,
+ * in `dtype`, >= 0 and finite, and are rounded to fp32 images.  With S_i = sum_t W_i(:,:,t) * rshift_t(H_i) (ReconstructFromDecomposition.m:30-38 per
+ * source) and S = sum_i S_i:
+ *   r_i = S_i ./ S,  q_i = r_i .^ power,  mask_i = q_i ./ sum_j q_j  where S > 0;   mask_i = 1 / num_sources  where S == 0;   Y_i = mask_i .* X
+ * The masks are formed in fp32 whatever dtype is, from the ratios r_i: scaling W or H by a power of two changes no bit of them.  X (m x n, column-major:
+ * `dtype` reals, or interleaved (re, im) pairs of them when is_complex != 0) never enters a mask; with NMFX_F64 only mask .* X runs in double.
+ *   output 0: out[i] receives Y_i, m x n elements of X's type;   output 1: out[i] receives mask_i, m x n reals of `dtype` (X may be NULL)
+ * NMFX_ERR_INVALID: a NULL pointer (K_s, W, H, out, an out[i]; X with output 0), a size or a K_s entry <= 0, power <= 0 or not finite, another dtype or
+ * output; NMFX_ERR_UNSUPPORTED: T > 64.  One GPU, one kernel launch, no atomics: two calls return the same bits.  The call holds
+ * m*n*(sizeof(X element) + num_sources * sizeof(out element)) + 4*K*(m*T + n) bytes; a failed allocation is NMFX_ERR_NOMEM.  Environment, read per call:
+ * NMFX_SOFTMASK_MAX_GRID lowers the workgroup count (tests), NMFX_SOFTMASK_FORM = register | sweep forces one of the kernel's two forms (register: at most
+ * 4 sources).  A new entry point; no structure grows, so NMFX_VERSION stays 600.  nmfx_last_call_timing describes the call. */
+nmfx_status nmfx_softmask(int64_t m, int64_t n, int32_t num_sources, const int32_t *K_s, int32_t T, int32_t dtype, int32_t is_complex, const void *X,
+                          const void *W, const void *H, double power, int32_t output, void *const *out, int32_t device);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,

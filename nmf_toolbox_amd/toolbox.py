@@ -1359,6 +1359,184 @@ def ReconstructFromDecomposition(W, H, device=0):
 reconstruct_from_decomposition = ReconstructFromDecomposition
 
 
+SOFTMASK_MAX_CONTEXT = 64
+
+
+def _softmask_factors(fn, W, H, cfg):
+    """W and H of softmask / softmask_batch as lists of per-source arrays (W_i as m x K_i x T) in float64 or their own float dtype: the lists nmf / cnmf /
+    wnmf / wcnmf return for several sources, or single arrays cut along K by config['sources']."""
+    if _is_cell(W) != _is_cell(H):
+        raise ValueError("%s: W and H must both be lists (one entry per source) or both be arrays (with config['sources'])" % fn)
+    def real(a, name):
+        a = np.asarray(a)
+        if a.dtype.kind not in "buif":
+            raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
+        return a if a.dtype.kind == "f" else a.astype(np.float64)
+    if _is_cell(W):
+        if len(W) != len(H):
+            raise ValueError("%s: W lists %d sources, H lists %d" % (fn, len(W), len(H)))
+        if len(W) == 0:
+            raise ValueError("%s: W and H list no source" % fn)
+        Wl, Hl = [real(w, "W") for w in W], [real(h, "H") for h in H]
+    else:
+        W, H = real(W, "W"), real(H, "H")
+        if W.ndim not in (2, 3) or H.ndim != 2:
+            raise ValueError("%s: W must be m x K or m x K x T and H must be K x n; got shapes %r and %r" % (fn, W.shape, H.shape))
+        K = W.shape[1]
+        src = cfg.get("sources", None)
+        if src is None:
+            raise ValueError("%s: W and H are single arrays: config['sources'] must say how the K = %d components split into sources "
+                             "(a list of positive integers summing to K, or 'components')" % (fn, K))
+        if isinstance(src, str):
+            if src != "components":
+                raise ValueError("%s: config['sources'] must be a list of positive integers summing to K, or 'components'; got %r" % (fn, src))
+            Ks = [1] * K
+        else:
+            try:
+                Ks = [int(k) for k in src]
+                ok = all(k > 0 and k == v for k, v in zip(Ks, src)) and len(Ks) > 0
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("%s: config['sources'] must be a list of positive integers summing to K, or 'components'; got %r" % (fn, src))
+            if sum(Ks) != K or H.shape[0] != K:
+                raise ValueError("%s: config['sources'] sums to %d, W has K = %d components and H has %d rows" % (fn, sum(Ks), K, H.shape[0]))
+        if H.shape[0] != K:
+            raise ValueError("%s: W has K = %d components, H has %d rows" % (fn, K, H.shape[0]))
+        off = np.concatenate([[0], np.cumsum(Ks)])
+        Wl = [W[:, off[i]:off[i + 1]] for i in range(len(Ks))]
+        Hl = [H[off[i]:off[i + 1]] for i in range(len(Ks))]
+    out = []
+    for i, w in enumerate(Wl):
+        if w.ndim == 2:
+            w = w.reshape(w.shape[0], w.shape[1], 1)
+        if w.ndim != 3:
+            raise ValueError("%s: W of source %d must be m x K_i or m x K_i x T; got shape %r" % (fn, i, w.shape))
+        out.append(w)
+    return out, Hl
+
+
+def _softmask_inputs(fn, X, W, H, config):
+    """Everything softmask checks before the library is touched, with `fn` in every message.  Returns X as it travels (float32, complex64, float64 or
+    complex128, column-major), W (m x K x T) and H (K x n) in X's real dtype with the sources side by side along K, [K_i], T, the power and the masks flag."""
+    cfg = config if config else {}
+    try:
+        _precision(cfg, fn)      # (raises for 'float64' / 'double': the masks are fp32 arithmetic, nothing runs silently in another precision)
+    except ValueError as e:
+        raise ValueError(str(e) if fn in str(e) else fn + ": " + str(e)) from None
+    if cfg.get("nmfx_gpus", None) is not None or cfg.get("nmfx_multi_backend", None) is not None:
+        raise ValueError("%s runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported" % fn)
+    power = cfg.get("power", 2.0)
+    if power is None:
+        power = 2.0
+    if isinstance(power, (str, bytes)) or not np.isscalar(power) or isinstance(power, complex):
+        raise ValueError("%s: power must be a positive finite number; got %r" % (fn, power))
+    power = float(power)
+    if not (power > 0.0) or not np.isfinite(power):
+        raise ValueError("%s: power must be a positive finite number; got %r" % (fn, power))
+    output = cfg.get("output", "estimates")
+    if not isinstance(output, str) or output not in ("estimates", "masks"):
+        raise ValueError("%s: output must be 'estimates' or 'masks'; got %r" % (fn, output))
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError("%s: X must be a matrix" % fn)
+    if X.dtype.kind not in "buifc":
+        raise ValueError("%s: X must be real or complex; got %s" % (fn, X.dtype))
+    if X.dtype not in (np.float32, np.complex64):
+        X = X.astype(np.complex128 if X.dtype.kind == "c" else np.float64)
+    rdt = np.float32 if X.dtype in (np.float32, np.complex64) else np.float64
+    m, n = X.shape
+    Wl, Hl = _softmask_factors(fn, W, H, cfg)
+    T = Wl[0].shape[2]
+    Ks = []
+    for i, (w, h) in enumerate(zip(Wl, Hl)):
+        if h.ndim != 2:
+            raise ValueError("%s: H of source %d must be a K_i x n matrix; got shape %r" % (fn, i, h.shape))
+        if w.shape[0] != m or h.shape[1] != n:
+            raise ValueError("%s: X is %d x %d, source %d has W with %d rows and H with %d columns" % (fn, m, n, i, w.shape[0], h.shape[1]))
+        if w.shape[1] != h.shape[0] or w.shape[1] < 1:
+            raise ValueError("%s: source %d has %d components in W and %d rows in H (K_i must agree and be >= 1)" % (fn, i, w.shape[1], h.shape[0]))
+        if w.shape[2] != T:
+            raise ValueError("%s: every source must have one context length T; source 0 has %d, source %d has %d" % (fn, T, i, w.shape[2]))
+        Ks.append(int(w.shape[1]))
+    if T < 1 or T > SOFTMASK_MAX_CONTEXT:
+        raise ValueError("%s: the context length T = %d is not supported (1 to %d)" % (fn, T, SOFTMASK_MAX_CONTEXT))
+    if m < 1 or n < 1:
+        raise ValueError("%s: X must not be empty; got %d x %d" % (fn, m, n))
+    with np.errstate(over="ignore"):     # (a float64 entry beyond float32's range is Inf in the fp32 image the device contracts, and refused)
+        Wc = np.asfortranarray(np.concatenate(Wl, axis=1), dtype=rdt)
+        Hc = np.asfortranarray(np.concatenate(Hl, axis=0), dtype=rdt)
+        for name, a in (("W", Wc), ("H", Hc)):
+            a32 = a if rdt == np.float32 else a.astype(np.float32)
+            if not np.all(np.isfinite(a32)):
+                raise ValueError("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name))
+            if a.size and a.min() < 0:
+                raise ValueError("%s: every entry of %s must be >= 0" % (fn, name))
+    return np.asfortranarray(X), Wc, Hc, Ks, T, power, output == "masks"
+
+
+def _softmask_c(X, Wc, Hc, Ks, T, power, masks, device):
+    """the one call into nmfx_softmask: X (m x n, the travelling dtype), Wc (m x K x T) and Hc (K x n) in its real dtype, column-major -> list of I arrays"""
+    m, n = X.shape
+    I = len(Ks)
+    cplx = X.dtype.kind == "c"
+    rdt = Wc.dtype
+    outs = [np.empty((m, n), dtype=rdt if masks else X.dtype, order="F") for _ in range(I)]
+    ks = np.asarray(Ks, dtype=np.int32)
+    ptrs = (C.c_void_p * I)(*[o.ctypes.data for o in outs])
+    lib = _lib.load()
+    _lib.check(lib.nmfx_softmask(m, n, I, _fptr(ks), T, _lib.F32 if rdt == np.float32 else _lib.F64, int(cplx), _fptr(X), _fptr(Wc), _fptr(Hc),
+                                 float(power), int(bool(masks)), C.cast(ptrs, C.c_void_p), int(device)))
+    return outs
+
+
+def softmask(X, W, H, config=None, device=0):
+    """Y = softmask(X, W, H, config): per-source estimates of the mixture X from a decomposition, by Wiener-style masks, in one fused pass.  An extension
+    (no reference .m).  For the sources i = 0 .. I-1 with W_i (m x K_i x T, or m x K_i when T == 1) and H_i (K_i x n), all >= 0 and finite:
+
+        S_i    = sum_t W_i(:,:,t) * rshift_t(H_i)        (ReconstructFromDecomposition.m:30-38 per source),   S = sum_i S_i
+        r_i    = S_i ./ S,   q_i = r_i .^ power          where S > 0
+        mask_i = q_i ./ sum_j q_j  where S > 0,   1/I  where S == 0 (no source has energy: the mixture is shared out evenly)
+        Y_i    = mask_i .* X                             X real or complex, m x n
+
+    W and H are the lists nmf / cnmf / wnmf / wcnmf return for several sources, or single arrays together with config['sources']: a list of positive
+    integers summing to K that cuts them along K, or 'components' (every component its own source).  Lists are taken as they are; 'sources' is then not
+    consulted.  Further config keys: 'power' (> 0, default 2: Wiener on a magnitude model; 1 is the ratio mask) and 'output' ('estimates', the default,
+    or 'masks').  Returns a list of I arrays, m x n.
+
+    float32 / complex64 X gives float32 / complex64 estimates; any other real or complex dtype travels as float64 / complex128.  The masks are fp32
+    device arithmetic on the fp32 images of W and H whatever X is (for a double X only mask .* X is done in double) and come back in X's real dtype.
+    They are formed from the ratios r_i: scaling W or H by a power of two changes no bit of them.  X never enters a mask, so a NaN or Inf in X stays in
+    its element.  T <= 64; n < T - 1 is allowed.  One GPU: nmfx_gpus, nmfx_multi_backend and nmfx_precision='float64' are refused."""
+    Xf, Wc, Hc, Ks, T, power, masks = _softmask_inputs("softmask", X, W, H, config)
+    return _softmask_c(Xf, Wc, Hc, Ks, T, power, masks, device)
+
+
+def softmask_batch(Xs, W, Hs, config=None, device=0):
+    """Ys = softmask_batch(Xs, W, Hs, config): softmask for B utterances Xs[b] (m x n_b) with their activations Hs[b] and ONE trained W (list or array, as
+    for softmask), in one call.  Ys[b] is the list softmask(Xs[b], W, Hs[b], config) returns, bit for bit, wherever b stands in the batch: the problems
+    travel side by side with T - 1 zero columns of H (and of X) between neighbours, so a shift never reads a neighbour's column.  Every Xs[b] must
+    travel in the same dtype.  config and the refusals are softmask's."""
+    fn = "softmask_batch"
+    if not _is_cell(Xs) or not _is_cell(Hs) or len(Xs) != len(Hs) or len(Xs) == 0:
+        raise ValueError("%s: Xs and Hs must be lists of the same length >= 1 (one entry per problem)" % fn)
+    probs = [_softmask_inputs(fn, X, W, H, config) for X, H in zip(Xs, Hs)]
+    X0, Wc, _, Ks, T, power, masks = probs[0]
+    for b, pr in enumerate(probs):
+        if pr[0].dtype != X0.dtype:
+            raise ValueError("%s: every Xs[b] must travel in one dtype; Xs[0] is %s, Xs[%d] is %s" % (fn, X0.dtype, b, pr[0].dtype))
+    m, K, gap = X0.shape[0], Wc.shape[1], T - 1
+    ns = [pr[0].shape[1] for pr in probs]
+    starts = np.concatenate([[0], np.cumsum([nb + gap for nb in ns])])[:-1]
+    N = int(starts[-1] + ns[-1])
+    Xcat, Hcat = np.zeros((m, N), dtype=X0.dtype, order="F"), np.zeros((K, N), dtype=Wc.dtype, order="F")
+    for pr, s0, nb in zip(probs, starts, ns):
+        Xcat[:, s0:s0 + nb] = pr[0]
+        Hcat[:, s0:s0 + nb] = pr[2]
+    outs = _softmask_c(Xcat, Wc, Hcat, Ks, T, power, masks, device)
+    return [[np.asfortranarray(o[:, s0:s0 + nb]) for o in outs] for s0, nb in zip(starts, ns)]
+
+
 def projfunc(s, k1, k2, nn=True, device=0):
     """[v, usediters] = projfunc(s, k1, k2, nn)  -- projfunc.m:1 (one vector)."""
     s = np.ascontiguousarray(np.asarray(s, dtype=np.float64).reshape(-1))
