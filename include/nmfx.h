@@ -301,6 +301,23 @@ nmfx_status nmfx_wcnmf_batch(const nmfx_problem *p, const void *M, int32_t batch
  * 4 sources).  A new entry point; no structure grows, so NMFX_VERSION stays 600.  nmfx_last_call_timing describes the call. */
 nmfx_status nmfx_softmask(int64_t m, int64_t n, int32_t num_sources, const int32_t *K_s, int32_t T, int32_t dtype, int32_t is_complex, const void *X,
                           const void *W, const void *H, double power, int32_t output, void *const *out, int32_t device);
+/* nmfx_softmask's pass on operands that already live on the device, asynchronous on `stream`: nothing is allocated, copied to or from the
+ * host or waited for, and nmfx_last_call_timing is left alone.  X_dev is an m x n view of float32 (is_complex == 0) or complex64 elements with a leading
+ * dimension, in either layout -- the element strides of (i, j):
+ *   layout 0, column-major: X[i + ldx*j], ldx >= m (the pass nmfx_softmask runs);   layout 1, row-major: X[i*ldx + j], ldx >= n (the MFMA operands change
+ *   places, so that every access to X and Y is still 32 consecutive elements: what a (freq, frames) spectrogram made on the device is)
+ * Y_dev receives num_sources outputs in X's layout with leading dimension ldy, output i beginning y_slab elements after output i - 1: complex64 / float32
+ * estimates (output 0) or float32 masks (output 1; X_dev may then be NULL and ldx is not read).  W_dev and H_dev are the fp32 images the kernel
+ * contracts, W[i + m*(t*K + k)] and H[k + K*j], >= 0 and finite (not checked here); koff_dev holds the first component of every source and K at the end
+ * (koff[0] = 0, increasing, koff[num_sources] = K; on the device, not checked here).  Both layouts give the same bits.
+ * NMFX_ERR_INVALID, before any device call: a NULL pointer (X_dev only with output 0), a size <= 0, K < num_sources, ldx or ldy below the contiguous
+ * extent, y_slab below one output (ldy * (n - 1) + m, or ldy * (m - 1) + n), power <= 0 or not finite, another layout or output; NMFX_ERR_UNSUPPORTED:
+ * T > 64.  NMFX_SOFTMASK_MAX_GRID and NMFX_SOFTMASK_FORM are read per call, as by nmfx_softmask.  A new entry point; no structure grows, so
+ * NMFX_VERSION stays 600. */
+nmfx_status nmfx_softmask_dev(void *stream, int64_t m, int64_t n, int32_t num_sources, const int32_t *koff_dev /* num_sources + 1, device */,
+                              int32_t K, int32_t T, int32_t is_complex, int32_t layout /* 0 column-major, 1 row-major */,
+                              const void *X_dev, int64_t ldx, const float *W_dev, const float *H_dev, double power, int32_t output,
+                              void *Y_dev, int64_t ldy, int64_t y_slab /* elements between the outputs of consecutive sources */, int32_t device);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,

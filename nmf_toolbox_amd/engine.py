@@ -489,3 +489,118 @@ def nmfsc_sharded(V, W, H, n_total=None, W_sparsity=0.0, H_sparsity=0.0, W_fixed
     info = dict(triesH=[int(t) for t in tH if t > 0], triesW=[int(t) for t in tW if t > 0], stepsizeH=r.stepsize_H, stepsizeW=r.stepsize_W,
                 converged_early=bool(r.converged_early), vmax=vmax, Vs=Vs)
     return cost[: r.cost_len].copy(), info
+
+
+_KOFF = {}   # (device, (K_0, ..., K_{I-1})) -> the int32 offsets on that device: a later call with the same split copies nothing
+
+
+def _softmask_images(W32, H32, dev):
+    """the two flat fp32 images the kernel reads, on `dev`, from per-source float32 tensors W_i (m x K_i x T) and H_i (K_i x n) with any strides:
+    W[i + m*(t*K + k)] is a contiguous (T, K, m) tensor, H[k + K*j] a contiguous (n, K) one"""
+    import torch
+    Wimg = torch.cat([w.to(dev).permute(2, 1, 0) for w in W32], dim=1).contiguous()
+    Himg = torch.cat([h.to(dev).t() for h in H32], dim=1).contiguous()
+    return Wimg, Himg
+
+
+def softmask(X, W, H, config=None):
+    """Y = engine.softmask(X, W, H, config): toolbox.softmask on a mixture that lives on the GPU, launched on torch's current stream of X's device; the
+    estimates (or masks) stay there.  Same definition, same kernel arithmetic and the same config keys ('power', 'output', 'sources').
+
+    X: a 2-D torch tensor, m x n, float32 or complex64, with one unit stride and the other at least the extent: row-major (stride (ld, 1): what
+    torch.stft returns per batch entry, and its column slices) or column-major (stride (1, ld): a .T view of a contiguous (n, m) tensor, as the Engine
+    keeps its buffers).  X is passed by pointer, never copied; the kernel has a form for either layout and both give the same bits.
+    W, H: lists per source, or single arrays with config['sources'], in natural shape (m x K_i x T or m x K_i, and K_i x n); every entry a numpy array or a
+    torch tensor on any device with any strides.  Their two fp32 images are built on X's device with torch ops, O((m*T + n)*K) elements.
+    config['nmfx_check'] (default True): check on the device that W and H are finite (as float32) and >= 0, which costs one host synchronisation; False
+    skips the check and the wait (numpy entries are always checked on the host).
+
+    Returns a list of I tensors on X's device, views of one (I, ...) allocation, in X's dtype (its real dtype for masks) and X's layout class, contiguous.
+    float64 / complex128 X is refused (toolbox.softmask serves them from the host); so are a 3-D X, X without a unit stride and conjugate views."""
+    import torch
+    from . import toolbox as TB
+    fn = "engine.softmask"
+    cfg = config if config else {}
+    power, masks = TB._softmask_config(fn, cfg)
+    check = cfg.get("nmfx_check", True)
+    if not isinstance(check, (bool, np.bool_)):
+        raise ValueError("%s: nmfx_check must be True or False; got %r" % (fn, check))
+    if not isinstance(X, torch.Tensor):
+        raise ValueError("%s: X must be a torch tensor (the host call softmask takes arrays); got %s" % (fn, type(X).__name__))
+    if X.dim() != 2:
+        raise ValueError("%s: X must be a matrix" % fn)
+    if not (X.is_floating_point() or X.is_complex() or X.dtype in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
+        raise ValueError("%s: X must be real or complex; got %s" % (fn, X.dtype))
+    m, n = int(X.shape[0]), int(X.shape[1])
+
+    def real(a, name):      # an entry of W or H: a torch tensor stays where it is, anything else goes the way softmask takes it
+        if isinstance(a, torch.Tensor):
+            if a.is_complex() or not (a.is_floating_point() or a.dtype in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
+                raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
+            return a.detach() if a.is_floating_point() else a.detach().to(torch.float64)
+        a = np.asarray(a)
+        if a.dtype.kind not in "buif":
+            raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
+        return a if a.dtype.kind == "f" else a.astype(np.float64)
+    Wl, Hl = TB._softmask_factors(fn, W, H, cfg, real=real)
+    Ks, T = TB._softmask_shapes(fn, m, n, Wl, Hl)
+    # the values, on the fp32 images the device contracts: numpy entries on the host as softmask checks them, torch entries where they live (one flag pair
+    # per device, read back together: the one synchronisation nmfx_check = False avoids)
+    W32, H32, flags = [], [], {}
+    for name, src, dst in (("W", Wl, W32), ("H", Hl, H32)):
+        for a in src:
+            if isinstance(a, torch.Tensor):
+                a32 = a.to(torch.float32)
+                if check and a32.numel():
+                    flags.setdefault(a32.device, []).append((name, torch.stack([~torch.isfinite(a32).all(), (a32 < 0).any()])))
+            else:
+                with np.errstate(over="ignore"):
+                    a32 = a.astype(np.float32, copy=False)
+                if not np.all(np.isfinite(a32)):
+                    raise ValueError("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name))
+                if a.size and a.min() < 0:
+                    raise ValueError("%s: every entry of %s must be >= 0" % (fn, name))
+                a32 = torch.from_numpy(np.ascontiguousarray(a32) if a32.flags.writeable else a32.copy())   # (torch takes no read-only array)
+            dst.append(a32)
+    for dev, fl in flags.items():
+        bad = torch.stack([f for _, f in fl]).cpu().numpy()
+        for (name, _), (notfinite, negative) in zip(fl, bad):
+            if notfinite:
+                raise ValueError("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name))
+            if negative:
+                raise ValueError("%s: every entry of %s must be >= 0" % (fn, name))
+    if X.dtype not in (torch.float32, torch.complex64):
+        raise ValueError("%s: X must be float32 or complex64 on the device; got %s.  The host call softmask serves float64 / complex128 (and every other "
+                         "dtype, as float64); nothing runs silently in another precision" % (fn, X.dtype))
+    s0, s1 = int(X.stride(0)), int(X.stride(1))
+    row_ok = (n == 1 or s1 == 1) and (m == 1 or s0 >= n)
+    col_ok = (m == 1 or s0 == 1) and (n == 1 or s1 >= m)
+    if row_ok and not (col_ok and s0 == 1 and s1 != 1):      # (a single row or column fits both: it is column-major only where its strides say (1, ld))
+        layout, ld = 1, (s0 if m > 1 else n)
+    elif col_ok:
+        layout, ld = 0, (s1 if n > 1 else m)
+    else:
+        raise ValueError("%s: X must have one unit stride and the other at least the extent, without overlap (row-major (ld, 1) with ld >= n, or column-major "
+                         "(1, ld) with ld >= m); got shape %r with strides %r -- pass X.contiguous()" % (fn, (m, n), (s0, s1)))
+    if X.is_conj() or X.is_neg():
+        raise ValueError("%s: X is a lazy conjugate or negative view: call .resolve_conj() (.resolve_neg()) on it first" % fn)
+    if not X.is_cuda:
+        raise _lib.NmfxError(_lib.NMFX_ERR_NO_DEVICE, "engine.softmask needs a CUDA/HIP tensor X: there is no CPU fallback")
+    dev, I, K = X.device, len(Ks), int(sum(Ks))
+    Wimg, Himg = _softmask_images(W32, H32, dev)
+    koff = _KOFF.get((dev, tuple(Ks)))
+    if koff is None:
+        koff = _KOFF[(dev, tuple(Ks))] = torch.tensor(np.concatenate([[0], np.cumsum(Ks)]), dtype=torch.int32).to(dev)
+    odt = torch.float32 if masks else X.dtype
+    if layout == 1:
+        out = torch.empty((I, m, n), dtype=odt, device=dev)
+        Y, ldy = [out[i] for i in range(I)], n
+    else:
+        out = torch.empty((I, n, m), dtype=odt, device=dev)
+        Y, ldy = [out[i].t() for i in range(I)], m
+    lib = _lib.load()
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib.nmfx_softmask_dev(stream, m, n, I, C.c_void_p(koff.data_ptr()), K, T, int(X.is_complex()), layout, C.c_void_p(X.data_ptr()), ld,
+                                     C.c_void_p(Wimg.data_ptr()), C.c_void_p(Himg.data_ptr()), float(power), int(masks), C.c_void_p(out.data_ptr()), ldy,
+                                     m * n, dev.index if dev.index is not None else torch.cuda.current_device()))
+    return Y

@@ -1362,16 +1362,18 @@ reconstruct_from_decomposition = ReconstructFromDecomposition
 SOFTMASK_MAX_CONTEXT = 64
 
 
-def _softmask_factors(fn, W, H, cfg):
+def _softmask_factors(fn, W, H, cfg, real=None):
     """W and H of softmask / softmask_batch as lists of per-source arrays (W_i as m x K_i x T) in float64 or their own float dtype: the lists nmf / cnmf /
-    wnmf / wcnmf return for several sources, or single arrays cut along K by config['sources']."""
+    wnmf / wcnmf return for several sources, or single arrays cut along K by config['sources'].  `real(a, name)` turns an entry into a real floating
+    array (engine.softmask passes one that also lets torch tensors through)."""
     if _is_cell(W) != _is_cell(H):
         raise ValueError("%s: W and H must both be lists (one entry per source) or both be arrays (with config['sources'])" % fn)
-    def real(a, name):
+    def real_numpy(a, name):
         a = np.asarray(a)
         if a.dtype.kind not in "buif":
             raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
         return a if a.dtype.kind == "f" else a.astype(np.float64)
+    real = real or real_numpy
     if _is_cell(W):
         if len(W) != len(H):
             raise ValueError("%s: W lists %d sources, H lists %d" % (fn, len(W), len(H)))
@@ -1416,10 +1418,8 @@ def _softmask_factors(fn, W, H, cfg):
     return out, Hl
 
 
-def _softmask_inputs(fn, X, W, H, config):
-    """Everything softmask checks before the library is touched, with `fn` in every message.  Returns X as it travels (float32, complex64, float64 or
-    complex128, column-major), W (m x K x T) and H (K x n) in X's real dtype with the sources side by side along K, [K_i], T, the power and the masks flag."""
-    cfg = config if config else {}
+def _softmask_config(fn, cfg):
+    """the checks of softmask's config keys -> (power, masks)"""
     try:
         _precision(cfg, fn)      # (raises for 'float64' / 'double': the masks are fp32 arithmetic, nothing runs silently in another precision)
     except ValueError as e:
@@ -1437,21 +1437,16 @@ def _softmask_inputs(fn, X, W, H, config):
     output = cfg.get("output", "estimates")
     if not isinstance(output, str) or output not in ("estimates", "masks"):
         raise ValueError("%s: output must be 'estimates' or 'masks'; got %r" % (fn, output))
-    X = np.asarray(X)
-    if X.ndim != 2:
-        raise ValueError("%s: X must be a matrix" % fn)
-    if X.dtype.kind not in "buifc":
-        raise ValueError("%s: X must be real or complex; got %s" % (fn, X.dtype))
-    if X.dtype not in (np.float32, np.complex64):
-        X = X.astype(np.complex128 if X.dtype.kind == "c" else np.float64)
-    rdt = np.float32 if X.dtype in (np.float32, np.complex64) else np.float64
-    m, n = X.shape
-    Wl, Hl = _softmask_factors(fn, W, H, cfg)
+    return power, output == "masks"
+
+
+def _softmask_shapes(fn, m, n, Wl, Hl):
+    """the per-source shape checks of softmask against an m x n mixture -> ([K_i], T)"""
     T = Wl[0].shape[2]
     Ks = []
     for i, (w, h) in enumerate(zip(Wl, Hl)):
         if h.ndim != 2:
-            raise ValueError("%s: H of source %d must be a K_i x n matrix; got shape %r" % (fn, i, h.shape))
+            raise ValueError("%s: H of source %d must be a K_i x n matrix; got shape %r" % (fn, i, tuple(h.shape)))
         if w.shape[0] != m or h.shape[1] != n:
             raise ValueError("%s: X is %d x %d, source %d has W with %d rows and H with %d columns" % (fn, m, n, i, w.shape[0], h.shape[1]))
         if w.shape[1] != h.shape[0] or w.shape[1] < 1:
@@ -1463,6 +1458,25 @@ def _softmask_inputs(fn, X, W, H, config):
         raise ValueError("%s: the context length T = %d is not supported (1 to %d)" % (fn, T, SOFTMASK_MAX_CONTEXT))
     if m < 1 or n < 1:
         raise ValueError("%s: X must not be empty; got %d x %d" % (fn, m, n))
+    return Ks, T
+
+
+def _softmask_inputs(fn, X, W, H, config):
+    """Everything softmask checks before the library is touched, with `fn` in every message.  Returns X as it travels (float32, complex64, float64 or
+    complex128, column-major), W (m x K x T) and H (K x n) in X's real dtype with the sources side by side along K, [K_i], T, the power and the masks flag."""
+    cfg = config if config else {}
+    power, masks = _softmask_config(fn, cfg)
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError("%s: X must be a matrix" % fn)
+    if X.dtype.kind not in "buifc":
+        raise ValueError("%s: X must be real or complex; got %s" % (fn, X.dtype))
+    if X.dtype not in (np.float32, np.complex64):
+        X = X.astype(np.complex128 if X.dtype.kind == "c" else np.float64)
+    rdt = np.float32 if X.dtype in (np.float32, np.complex64) else np.float64
+    m, n = X.shape
+    Wl, Hl = _softmask_factors(fn, W, H, cfg)
+    Ks, T = _softmask_shapes(fn, m, n, Wl, Hl)
     with np.errstate(over="ignore"):     # (a float64 entry beyond float32's range is Inf in the fp32 image the device contracts, and refused)
         Wc = np.asfortranarray(np.concatenate(Wl, axis=1), dtype=rdt)
         Hc = np.asfortranarray(np.concatenate(Hl, axis=0), dtype=rdt)
@@ -1472,7 +1486,7 @@ def _softmask_inputs(fn, X, W, H, config):
                 raise ValueError("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name))
             if a.size and a.min() < 0:
                 raise ValueError("%s: every entry of %s must be >= 0" % (fn, name))
-    return np.asfortranarray(X), Wc, Hc, Ks, T, power, output == "masks"
+    return np.asfortranarray(X), Wc, Hc, Ks, T, power, masks
 
 
 def _softmask_c(X, Wc, Hc, Ks, T, power, masks, device):
