@@ -13,9 +13,11 @@
 //   H step: nb_pass<CONV> with the window rows of 64 columns stationary and all rows of WC_b streamed: Q = WC'*A (and WC'*S) to a K*T x N buffer, then
 //           cb_hupdate: gradient(k, j) = sum_t Q((T-1-t)K + k, j + t) over j + t < n_b, in t order (cnmf.m:217-226), and cnmf.m:231.
 //           KL keeps the reference's quirk: V_pos is not shifted (cnmf.m:220-221), the denominator is sum_t colsum(W_t)(k) for every column.
-// One iteration = nb_pass<W step> -> nb_decide -> cb_wupdate -> nb_pass<H step> -> cb_hupdate, plain launches on one stream; work of a problem with done[b] != 0
-// returns at once.  A problem's items, chunks and summation orders follow from its own (m, n_b, K, T); no sum that reaches a result uses an atomic.
+// The launch sequence is nb_driver.h's, with cb_wupdate between the two passes and cb_hupdate after the H-step pass; here are the kernels that are
+// cnmf_batch's own and its variant of the driver.  A problem's items, chunks and summation orders follow from its own (m, n_b, K, T); no sum that reaches a
+// result uses an atomic.
 #include "nb_pass.h"
+#include "nb_driver.h"
 
 namespace nmfx {
 namespace {
@@ -157,147 +159,26 @@ __global__ __launch_bounds__(256) void cb_hupdate(const CbHup g) {
     }
 }
 
-nmfx_status run_cnmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *off, nmfx_result *r, int32_t *cost_len) {
-    TRY(validate_problem(p, r, false, true));
-    if (!off || !cost_len) { set_error("cnmf_batch: col_offsets and cost_len are required"); return NMFX_ERR_INVALID; }
-    if (batch < 1) { set_error("cnmf_batch: batch = %d, must be >= 1", batch); return NMFX_ERR_INVALID; }
-    if (off[0] != 0) { set_error("cnmf_batch: col_offsets[0] must be 0"); return NMFX_ERR_INVALID; }
-    for (int b = 0; b < batch; ++b) {
-        const long long nb = (long long)(off[b + 1] - off[b]);
-        if (nb <= 0 || nb > 0x7fffffffLL) { set_error("cnmf_batch: col_offsets must increase (problem %d has %lld columns)", b, nb); return NMFX_ERR_INVALID; }
-        if (nb < p->T - 1) { set_error("cnmf_batch: problem %d has %lld columns, fewer than T - 1 = %d (cnmf.m:188 has no H_shifted there)", b, nb, p->T - 1); return NMFX_ERR_INVALID; }
-    }
-    if (off[batch] != p->n) { set_error("cnmf_batch: col_offsets[batch] = %lld != n = %lld", (long long)off[batch], (long long)p->n); return NMFX_ERR_INVALID; }
-    if (p->num_sources != 1) { set_error("cnmf_batch: num_sources must be 1 (num_sources = %d)", p->num_sources); return NMFX_ERR_UNSUPPORTED; }
-    int div;
-    switch (p->divergence) {
-        case NMFX_DIV_EUCLIDEAN: div = NB_EUC; break;
-        case NMFX_DIV_KL: div = NB_KL; break;
-        default: set_error("cnmf_batch has the euclidean and kl divergences only (divergence = %d)", p->divergence); return NMFX_ERR_UNSUPPORTED;
-    }
-    if (p->n_gpus > 1 || p->multi_backend != 0) { set_error("cnmf_batch: one GPU only (n_gpus = %d, multi_backend = %d)", p->n_gpus, p->multi_backend); return NMFX_ERR_UNSUPPORTED; }
-    if ((long)p->K_total * p->T > 256) { set_error("cnmf_batch: K * T = %ld, at most 256 is supported", (long)p->K_total * p->T); return NMFX_ERR_UNSUPPORTED; }
-    const long m = p->m, N = p->n;
-    const int K = p->K_total, T = p->T, KT = K * T, KP = nb_kp(KT), B = batch, maxiter = p->maxiter;
-    const double lamW = p->W_sparsity ? p->W_sparsity[0] : 0.0, lamH = p->H_sparsity ? p->H_sparsity[0] : 0.0;
-    const bool fixW = p->W_fixed && p->W_fixed[0], fixH = p->H_fixed && p->H_fixed[0];
-    // the work tables: a problem's items follow from its own shape
-    std::vector<NbProb> prob(B);
-    const int ntr = (int)((m + NB_T - 1) / NB_T);
-    long wi = 0, hi = 0;
-    for (int b = 0; b < B; ++b) {
-        NbProb &q = prob[b];
-        q.col0 = off[b]; q.n = (int)(off[b + 1] - off[b]); q.nc = (q.n + NB_CHUNK - 1) / NB_CHUNK; q.ntr = ntr; q.pad_ = 0;
-        if (wi > 0x7fffffffL || hi > 0x7fffffffL) break;
-        q.witem0 = (int)wi; q.hitem0 = (int)hi;
-        wi += (long)q.nc * ntr; hi += (q.n + NB_T - 1) / NB_T;
-    }
-    if (wi > 0x7fffffffL || hi > 0x7fffffffL) { set_error("cnmf_batch: too many work items (%ld, %ld)", wi, hi); return NMFX_ERR_UNSUPPORTED; }
-    std::vector<int> wtab((size_t)wi), htab((size_t)hi);
-    for (int b = 0; b < B; ++b) {
-        std::fill(wtab.begin() + prob[b].witem0, wtab.begin() + prob[b].witem0 + (long)prob[b].nc * ntr, b);
-        std::fill(htab.begin() + prob[b].hitem0, htab.begin() + prob[b].hitem0 + (prob[b].n + NB_T - 1) / NB_T, b);
-    }
-    DeviceGuard dg_;
-    TRY(check_device(p->device));
-    PooledStream ps{p->device};
-    TRY(pool_stream(p->device, &ps.st));
-    hipStream_t st = ps.st;
-    const size_t mN = (size_t)m * N, KN = (size_t)K * N, KTN = (size_t)KT * N, mKTB = (size_t)m * KT * B;
-    const size_t slabsz = (size_t)(div == NB_EUC ? 2 : 1) * KP * NB_T;
-    DevBuf Vd, Hm, Wm, WC, Qb, Pb, slab, cpart, cw, dcost, ddone, dprob, dwtab, dhtab, tmp32;
-    TRY(Vd.alloc(mN * 4)); TRY(Hm.alloc(KN * 8)); TRY(Wm.alloc(mKTB * 8)); TRY(WC.alloc(mKTB * 8));
-    TRY(slab.alloc(fixW ? 0 : (size_t)wi * slabsz * 8)); TRY(cpart.alloc((size_t)wi * 8)); TRY(cw.alloc((size_t)K * B * 8));
-    TRY(dcost.alloc((size_t)maxiter * B * 8)); TRY(ddone.alloc((size_t)B * 4)); TRY(dprob.alloc((size_t)B * sizeof(NbProb)));
-    TRY(dwtab.alloc((size_t)wi * 4)); TRY(dhtab.alloc((size_t)hi * 4));
-    if (!fixH) { TRY(Qb.alloc(KTN * 8)); if (div == NB_EUC) TRY(Pb.alloc(KTN * 8)); }
-    if (p->dtype == NMFX_F32) TRY(tmp32.alloc(std::max(mKTB, KN) * 4));
-    std::vector<int> hdone(B, 0);
-    StreamDrain drain_(st);
-    CallClock clock;
-    NMFX_HIP(hipMemcpyAsync(dprob.p, prob.data(), (size_t)B * sizeof(NbProb), hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(dwtab.p, wtab.data(), (size_t)wi * 4, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(dhtab.p, htab.data(), (size_t)hi * 4, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemsetAsync(ddone.p, 0, (size_t)B * 4, st));
-    NMFX_HIP(hipMemsetAsync(dcost.p, 0, (size_t)maxiter * B * 8, st));
-    TRY(upload(st, p->V, p->dtype, Vd.as<float>(), mN, 1.0));
-    TRY(ingest64(st, p->W_init, p->dtype, Wm.as<double>(), mKTB, tmp32));
-    NMFX_HIP(hipStreamSynchronize(st));   // (the staging buffer is reused)
-    TRY(ingest64(st, p->H_init, p->dtype, Hm.as<double>(), KN, tmp32));
-    NMFX_HIP(hipStreamSynchronize(st));   // (the caller's pageable buffers and the host tables have been read)
-    clock.end(&IoStats::ingest_s);
-
-    const long cols = (long)K * B;
-    hipLaunchKernelGGL(cb_winit, dim3(grid_of(cols)), dim3(256), 0, st, dprob.as<NbProb>(), Wm.as<double>(), WC.as<double>(), cw.as<double>(), Hm.as<double>(), m, K, T, cols);   // cnmf.m:157-166
-    NMFX_HIP(hipGetLastError());
-    NbPass wp{};
-    wp.prob = dprob.as<NbProb>(); wp.tab = dwtab.as<int>(); wp.items = (int)wi; wp.done = ddone.as<int>(); wp.V = Vd.as<float>(); wp.m = m; wp.K = KT;
-    wp.WT = WC.as<double>(); wp.slab = slab.as<double>(); wp.costpart = cpart.as<double>(); wp.Hm = Hm.as<double>();
-    wp.cw = cw.as<double>(); wp.lamH = lamH; wp.Pbuf = Pb.as<double>(); wp.Qbuf = Qb.as<double>(); wp.Kb = K; wp.T = T;
-    NbPass hp = wp;
-    hp.tab = dhtab.as<int>(); hp.items = (int)hi;
-    NbDecide dd{};
-    dd.prob = dprob.as<NbProb>(); dd.B = B; dd.done = ddone.as<int>(); dd.costpart = cpart.as<double>(); dd.cost = dcost.as<double>(); dd.maxiter = maxiter;
-    dd.tol = p->tolerance; dd.scale = div == NB_EUC ? 0.5 : 1.0; dd.lamW = lamW; dd.lamH = lamH; dd.Wm = Wm.as<double>(); dd.Hm = Hm.as<double>(); dd.wlen = m * KT; dd.K = K;
+// nb_drive's variant (nb_driver.h)
+struct CnmfBatch {
+    static constexpr bool CONV = true, WGT = false;
+    static constexpr const char *NAME = "cnmf_batch";
     CbWup wu{};
-    wu.prob = dprob.as<NbProb>(); wu.done = ddone.as<int>(); wu.slab = slab.as<double>(); wu.Wm = Wm.as<double>(); wu.WC = WC.as<double>(); wu.Hm = Hm.as<double>();
-    wu.cw = cw.as<double>(); wu.m = m; wu.cols = cols; wu.K = K; wu.T = T; wu.KP = KP; wu.euc = div == NB_EUC; wu.lamW = lamW;
     CbHup hu{};
-    hu.prob = dprob.as<NbProb>(); hu.tab = dhtab.as<int>(); hu.items = (int)hi; hu.done = ddone.as<int>(); hu.Q = Qb.as<double>(); hu.P = Pb.as<double>();
-    hu.cw = cw.as<double>(); hu.Hm = Hm.as<double>(); hu.K = K; hu.T = T; hu.euc = div == NB_EUC; hu.lamH = lamH;
-    auto decide = [&](int idx, int final) -> nmfx_status {
-        dd.idx = idx; dd.final = final;
-        hipLaunchKernelGGL(nb_decide, dim3(grid_of(B)), dim3(256), 0, st, dd);
-        NMFX_HIP(hipGetLastError());
-        return NMFX_OK;
-    };
-    bool all_done = false;
-    for (int it = 0; it < maxiter; ++it) {
-        // the pass that opens iteration it + 1: the W-step sums of (W(it), H(it)) and, from the second iteration on, the cost of iteration it
-        wp.cost_only = fixW;
-        if (!fixW || it > 0) TRY(nb_run_pass<true>(st, wp, div, false));
-        if (it > 0) {
-            TRY(decide(it - 1, 0));
-            if (p->tolerance >= 0 && it % 16 == 0) {   // nobody left to iterate?
-                NMFX_HIP(hipMemcpyAsync(hdone.data(), ddone.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-                NMFX_HIP(hipStreamSynchronize(st));
-                all_done = std::all_of(hdone.begin(), hdone.end(), [](int d) { return d != 0; });
-                if (all_done) break;
-            }
-        }
-        if (!fixW) {
-            hipLaunchKernelGGL(cb_wupdate, dim3(grid_of(cols)), dim3(256), 0, st, wu);
-            NMFX_HIP(hipGetLastError());
-        }
-        if (!fixH) {
-            TRY(nb_run_pass<true>(st, hp, div, true));
-            hipLaunchKernelGGL(cb_hupdate, dim3(grid_of(hi)), dim3(256), 0, st, hu);
-            NMFX_HIP(hipGetLastError());
-        }
+    nmfx_status init(hipStream_t st, const NbState &s) {
+        wu.prob = s.prob; wu.done = s.done; wu.slab = s.slab; wu.Wm = s.Wm; wu.WC = s.WT; wu.Hm = s.Hm;
+        wu.cw = s.cw; wu.m = s.m; wu.cols = s.cols; wu.K = s.K; wu.T = s.T; wu.KP = s.KP; wu.euc = s.euc; wu.lamW = s.lamW;
+        hu.prob = s.prob; hu.tab = s.htab; hu.items = s.hitems; hu.done = s.done; hu.Q = s.Q; hu.P = s.P;
+        hu.cw = s.cw; hu.Hm = s.Hm; hu.K = s.K; hu.T = s.T; hu.euc = s.euc; hu.lamH = s.lamH;
+        return nb_each(cb_winit, s.cols, st, s.prob, s.Wm, s.WT, s.cw, s.Hm, s.m, s.K, s.T, s.cols);
     }
-    if (!all_done) {   // cnmf.m:236-251 of the last iteration, for the problems still running
-        wp.cost_only = 1;
-        TRY(nb_run_pass<true>(st, wp, div, false));
-        TRY(decide(maxiter - 1, 1));
-    }
-    NMFX_HIP(hipMemcpyAsync(hdone.data(), ddone.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    NMFX_HIP(hipMemcpyAsync(r->cost, dcost.p, (size_t)maxiter * B * 8, hipMemcpyDeviceToHost, st));
-    NMFX_HIP(hipStreamSynchronize(st));
-    int longest = 0;
-    for (int b = 0; b < B; ++b) { cost_len[b] = hdone[b]; longest = std::max(longest, hdone[b]); }
-    r->cost_len = r->iters_run = longest;
-    clock.end(&IoStats::iterate_s);
-    TRY(egress64(st, Wm.as<double>(), p->dtype, r->W, mKTB, tmp32));
-    NMFX_HIP(hipStreamSynchronize(st));
-    TRY(egress64(st, Hm.as<double>(), p->dtype, r->H, KN, tmp32));
-    NMFX_HIP(hipStreamSynchronize(st));
-    clock.end(&IoStats::egress_s);
-    return NMFX_OK;
-}
+    nmfx_status wupdate(hipStream_t st) { return nb_each(cb_wupdate, wu.cols, st, wu); }
+    nmfx_status hupdate(hipStream_t st) { return nb_each(cb_hupdate, hu.items, st, hu); }
+};
 
 }  // namespace
 }  // namespace nmfx
 
 extern "C" nmfx_status nmfx_cnmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *col_offsets, nmfx_result *r, int32_t *cost_len) {
-    return nmfx::run_cnmf_batch(p, batch, col_offsets, r, cost_len);
+    return nmfx::nb_drive<nmfx::CnmfBatch>(p, nullptr, batch, col_offsets, r, cost_len);
 }

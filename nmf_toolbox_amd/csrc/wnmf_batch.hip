@@ -10,12 +10,12 @@
 // second kind (A and B), so the kl step has the euclidean step's two accumulator sets, its doubled slabs and its two launches at KP = 256; the kl denominators
 // of both updates are contractions here (B*H_b', W_b'*B), where nmf_batch has rowsum(H_b) and colsum(W_b).
 //
-// The pass kernel is nb_pass.h's with WGT = true: this file instantiates only those, nmf_batch.hip and cnmf_batch.hip keep theirs.  One iteration = four plain
-// launches on one stream for the whole batch (five or six at KP = 256), as in nmf_batch.hip:
-//     nb_pass<W step>  ->  nb_decide (cost(t-1), the stop rule, done[b])  ->  wb_wupdate  ->  nb_pass<H step>
-// and after the last iteration one cost-only W-step pass and one nb_decide.  A problem's tiles, chunks and summation orders depend on its own shape alone and
-// no sum that reaches a result uses an atomic: its result is bit-identical wherever it sits in the batch and from run to run.
+// The pass kernel is nb_pass.h's with WGT = true: this file instantiates only those, nmf_batch.hip and cnmf_batch.hip keep theirs.  The launch sequence is
+// nb_driver.h's (four plain launches per iteration, five or six at KP = 256, wb_wupdate between the two passes); here are the kernels that are wnmf_batch's
+// own and its variant of the driver.  A problem's tiles, chunks and summation orders depend on its own shape alone and no sum that reaches a result uses an
+// atomic: its result is bit-identical wherever it sits in the batch and from run to run.
 #include "nb_pass.h"
+#include "nb_driver.h"
 
 namespace nmfx {
 namespace {
@@ -96,140 +96,22 @@ __global__ __launch_bounds__(256) void wb_wupdate(const WbWup g) {
     }
 }
 
-nmfx_status run_wnmf_batch(const nmfx_problem *p, const void *M, int32_t batch, const int64_t *off, nmfx_result *r, int32_t *cost_len) {
-    TRY(validate_problem(p, r, false, true));
-    if (!M) { set_error("wnmf_batch: the weights M are required"); return NMFX_ERR_INVALID; }
-    if (!off || !cost_len) { set_error("wnmf_batch: col_offsets and cost_len are required"); return NMFX_ERR_INVALID; }
-    if (batch < 1) { set_error("wnmf_batch: batch = %d, must be >= 1", batch); return NMFX_ERR_INVALID; }
-    if (off[0] != 0) { set_error("wnmf_batch: col_offsets[0] must be 0"); return NMFX_ERR_INVALID; }
-    for (int b = 0; b < batch; ++b)
-        if (off[b + 1] <= off[b] || off[b + 1] - off[b] > 0x7fffffffL) { set_error("wnmf_batch: col_offsets must increase (problem %d has %lld columns)", b, (long long)(off[b + 1] - off[b])); return NMFX_ERR_INVALID; }
-    if (off[batch] != p->n) { set_error("wnmf_batch: col_offsets[batch] = %lld != n = %lld", (long long)off[batch], (long long)p->n); return NMFX_ERR_INVALID; }
-    if (p->T != 1 || p->num_sources != 1) { set_error("wnmf_batch: T and num_sources must be 1 (T = %d, num_sources = %d)", p->T, p->num_sources); return NMFX_ERR_UNSUPPORTED; }
-    int div;
-    switch (p->divergence) {
-        case NMFX_DIV_EUCLIDEAN: div = NB_EUC; break;
-        case NMFX_DIV_KL: div = NB_KL; break;
-        case NMFX_DIV_IS: case NMFX_DIV_AB: set_error("wnmf_batch has the euclidean and kl divergences only (divergence = %d)", p->divergence); return NMFX_ERR_UNSUPPORTED;
-        default: set_error("wnmf_batch: divergence %d has no update equations (nmf.m:165-166)", p->divergence); return NMFX_ERR_INVALID;
-    }
-    if (p->n_gpus > 1 || p->multi_backend != 0) { set_error("wnmf_batch: one GPU only (n_gpus = %d, multi_backend = %d)", p->n_gpus, p->multi_backend); return NMFX_ERR_UNSUPPORTED; }
-    if (p->K_total > 256) { set_error("wnmf_batch: K = %d, at most 256 is supported", p->K_total); return NMFX_ERR_UNSUPPORTED; }
-    const long m = p->m, N = p->n;
-    const int K = p->K_total, KP = nb_kp(K), B = batch, maxiter = p->maxiter;
-    const double lamW = p->W_sparsity ? p->W_sparsity[0] : 0.0, lamH = p->H_sparsity ? p->H_sparsity[0] : 0.0;
-    const bool fixW = p->W_fixed && p->W_fixed[0], fixH = p->H_fixed && p->H_fixed[0];
-    // the work tables: a problem's items follow from its own shape
-    std::vector<NbProb> prob(B);
-    const int ntr = (int)((m + NB_T - 1) / NB_T);
-    long wi = 0, hi = 0;
-    for (int b = 0; b < B; ++b) {
-        NbProb &q = prob[b];
-        q.col0 = off[b]; q.n = (int)(off[b + 1] - off[b]); q.nc = (q.n + NB_CHUNK - 1) / NB_CHUNK; q.ntr = ntr; q.pad_ = 0;
-        if (wi > 0x7fffffffL || hi > 0x7fffffffL) break;
-        q.witem0 = (int)wi; q.hitem0 = (int)hi;
-        wi += (long)q.nc * ntr; hi += (q.n + NB_T - 1) / NB_T;
-    }
-    if (wi > 0x7fffffffL || hi > 0x7fffffffL) { set_error("wnmf_batch: too many work items (%ld, %ld)", wi, hi); return NMFX_ERR_UNSUPPORTED; }
-    std::vector<int> wtab((size_t)wi), htab((size_t)hi);
-    for (int b = 0; b < B; ++b) {
-        std::fill(wtab.begin() + prob[b].witem0, wtab.begin() + prob[b].witem0 + (long)prob[b].nc * ntr, b);
-        std::fill(htab.begin() + prob[b].hitem0, htab.begin() + prob[b].hitem0 + (prob[b].n + NB_T - 1) / NB_T, b);
-    }
-    DeviceGuard dg_;
-    TRY(check_device(p->device));
-    PooledStream ps{p->device};
-    TRY(pool_stream(p->device, &ps.st));
-    hipStream_t st = ps.st;
-    const size_t mN = (size_t)m * N, KN = (size_t)K * N, mKB = (size_t)m * K * B;
-    const size_t slabsz = (size_t)2 * KP * NB_T;   // N and P, both divergences
-    DevBuf Vd, Md, Hm, Wm, WT, Pb, slab, cpart, dcost, ddone, dprob, dwtab, dhtab, tmp32;
-    TRY(Vd.alloc(mN * 4)); TRY(Md.alloc(mN * 4)); TRY(Hm.alloc(KN * 8)); TRY(Wm.alloc(mKB * 8)); TRY(WT.alloc(mKB * 8));
-    TRY(slab.alloc(fixW ? 0 : (size_t)wi * slabsz * 8)); TRY(cpart.alloc((size_t)wi * 8));
-    TRY(dcost.alloc((size_t)maxiter * B * 8)); TRY(ddone.alloc((size_t)B * 4)); TRY(dprob.alloc((size_t)B * sizeof(NbProb)));
-    TRY(dwtab.alloc((size_t)wi * 4)); TRY(dhtab.alloc((size_t)hi * 4));
-    if (nb_two_launches(KP, true) && !fixH) TRY(Pb.alloc(KN * 8));   // (the H step is two launches there)
-    if (p->dtype == NMFX_F32) TRY(tmp32.alloc(std::max(mKB, KN) * 4));
-    std::vector<int> hdone(B, 0);
-    StreamDrain drain_(st);
-    CallClock clock;
-    NMFX_HIP(hipMemcpyAsync(dprob.p, prob.data(), (size_t)B * sizeof(NbProb), hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(dwtab.p, wtab.data(), (size_t)wi * 4, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(dhtab.p, htab.data(), (size_t)hi * 4, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemsetAsync(ddone.p, 0, (size_t)B * 4, st));
-    NMFX_HIP(hipMemsetAsync(dcost.p, 0, (size_t)maxiter * B * 8, st));
-    TRY(upload(st, p->V, p->dtype, Vd.as<float>(), mN, 1.0));
-    TRY(upload(st, M, p->dtype, Md.as<float>(), mN, 1.0));
-    TRY(ingest64(st, p->W_init, p->dtype, Wm.as<double>(), mKB, tmp32));
-    NMFX_HIP(hipStreamSynchronize(st));   // (the staging buffer is reused)
-    TRY(ingest64(st, p->H_init, p->dtype, Hm.as<double>(), KN, tmp32));
-    NMFX_HIP(hipStreamSynchronize(st));   // (the caller's pageable buffers and the host tables have been read)
-    clock.end(&IoStats::ingest_s);
-
-    const long cols = (long)K * B;
-    hipLaunchKernelGGL(wb_wnorm, dim3(grid_of(cols)), dim3(256), 0, st, Wm.as<double>(), WT.as<double>(), m, K, cols);   // nmf.m:130-134
-    NMFX_HIP(hipGetLastError());
-    NbPass wp{};
-    wp.prob = dprob.as<NbProb>(); wp.tab = dwtab.as<int>(); wp.items = (int)wi; wp.done = ddone.as<int>(); wp.V = Vd.as<float>(); wp.M = Md.as<float>(); wp.m = m; wp.K = K;
-    wp.WT = WT.as<double>(); wp.slab = slab.as<double>(); wp.costpart = cpart.as<double>(); wp.Hm = Hm.as<double>();
-    wp.lamH = lamH; wp.Pbuf = Pb.as<double>();
-    NbPass hp = wp;
-    hp.tab = dhtab.as<int>(); hp.items = (int)hi;
-    NbDecide dd{};
-    dd.prob = dprob.as<NbProb>(); dd.B = B; dd.done = ddone.as<int>(); dd.costpart = cpart.as<double>(); dd.cost = dcost.as<double>(); dd.maxiter = maxiter;
-    dd.tol = p->tolerance; dd.scale = div == NB_EUC ? 0.5 : 1.0; dd.lamW = lamW; dd.lamH = lamH; dd.Wm = Wm.as<double>(); dd.Hm = Hm.as<double>(); dd.wlen = m * K; dd.K = K;
+// nb_drive's variant (nb_driver.h)
+struct WnmfBatch {
+    static constexpr bool CONV = false, WGT = true;
+    static constexpr const char *NAME = "wnmf_batch";
     WbWup wu{};
-    wu.prob = dprob.as<NbProb>(); wu.done = ddone.as<int>(); wu.slab = slab.as<double>(); wu.Wm = Wm.as<double>(); wu.WT = WT.as<double>();
-    wu.m = m; wu.cols = cols; wu.K = K; wu.KP = KP; wu.lamW = lamW;
-    auto decide = [&](int idx, int final) -> nmfx_status {
-        dd.idx = idx; dd.final = final;
-        hipLaunchKernelGGL(nb_decide, dim3(grid_of(B)), dim3(256), 0, st, dd);
-        NMFX_HIP(hipGetLastError());
-        return NMFX_OK;
-    };
-    bool all_done = false;
-    for (int it = 0; it < maxiter; ++it) {
-        // the pass that opens iteration it + 1: the W-step sums of (W(it), H(it)) and, from the second iteration on, the cost of iteration it
-        wp.cost_only = fixW;
-        if (!fixW || it > 0) TRY((nb_run_pass<false, true>(st, wp, div, false)));
-        if (it > 0) {
-            TRY(decide(it - 1, 0));
-            if (p->tolerance >= 0 && it % 16 == 0) {   // nobody left to iterate?
-                NMFX_HIP(hipMemcpyAsync(hdone.data(), ddone.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-                NMFX_HIP(hipStreamSynchronize(st));
-                all_done = std::all_of(hdone.begin(), hdone.end(), [](int d) { return d != 0; });
-                if (all_done) break;
-            }
-        }
-        if (!fixW) {
-            hipLaunchKernelGGL(wb_wupdate, dim3(grid_of(cols)), dim3(256), 0, st, wu);
-            NMFX_HIP(hipGetLastError());
-        }
-        if (!fixH) TRY((nb_run_pass<false, true>(st, hp, div, true)));
+    nmfx_status init(hipStream_t st, const NbState &s) {
+        wu.prob = s.prob; wu.done = s.done; wu.slab = s.slab; wu.Wm = s.Wm; wu.WT = s.WT;
+        wu.m = s.m; wu.cols = s.cols; wu.K = s.K; wu.KP = s.KP; wu.lamW = s.lamW;
+        return nb_each(wb_wnorm, s.cols, st, s.Wm, s.WT, s.m, s.K, s.cols);
     }
-    if (!all_done) {   // nmf.m:203-218 of the last iteration, for the problems still running
-        wp.cost_only = 1;
-        TRY((nb_run_pass<false, true>(st, wp, div, false)));
-        TRY(decide(maxiter - 1, 1));
-    }
-    NMFX_HIP(hipMemcpyAsync(hdone.data(), ddone.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    NMFX_HIP(hipMemcpyAsync(r->cost, dcost.p, (size_t)maxiter * B * 8, hipMemcpyDeviceToHost, st));
-    NMFX_HIP(hipStreamSynchronize(st));
-    int longest = 0;
-    for (int b = 0; b < B; ++b) { cost_len[b] = hdone[b]; longest = std::max(longest, hdone[b]); }
-    r->cost_len = r->iters_run = longest;
-    clock.end(&IoStats::iterate_s);
-    TRY(egress64(st, Wm.as<double>(), p->dtype, r->W, mKB, tmp32));
-    NMFX_HIP(hipStreamSynchronize(st));
-    TRY(egress64(st, Hm.as<double>(), p->dtype, r->H, KN, tmp32));
-    NMFX_HIP(hipStreamSynchronize(st));
-    clock.end(&IoStats::egress_s);
-    return NMFX_OK;
-}
+    nmfx_status wupdate(hipStream_t st) { return nb_each(wb_wupdate, wu.cols, st, wu); }
+};
 
 }  // namespace
 }  // namespace nmfx
 
 extern "C" nmfx_status nmfx_wnmf_batch(const nmfx_problem *p, const void *M, int32_t batch, const int64_t *col_offsets, nmfx_result *r, int32_t *cost_len) {
-    return nmfx::run_wnmf_batch(p, M, batch, col_offsets, r, cost_len);
+    return nmfx::nb_drive<nmfx::WnmfBatch>(p, M, batch, col_offsets, r, cost_len);
 }

@@ -368,6 +368,139 @@ def wcnmf(V, M, num_basis_elems, context_len, config=None, device=0):
 _DIV_BATCH = {"euclidean": _lib.DIV_EUCLIDEAN, "kl_divergence": _lib.DIV_KL, "kl": _lib.DIV_KL}
 
 
+def _batch(fn, Vs, Ms, num_basis_elems, context_len, config, device):
+    """The one body of nmf_batch, wnmf_batch, cnmf_batch and wcnmf_batch (fn: the call's name, for its messages and its entry nmfx_<fn>): the checks in
+    their order, the config clamping, the problems packed side by side along the columns, one library call, the results cut apart again.  Ms is None for
+    the unweighted calls and context_len is None for the plain ones; which family a call belongs to follows from fn, not from a None handed in by a caller."""
+    conv, weighted = fn in ("cnmf_batch", "wcnmf_batch"), fn in ("wnmf_batch", "wcnmf_batch")
+    cfg = dict(config) if config else {}
+    if fn == "nmf_batch":
+        _precision(cfg, fn)       # nmf_batch only: "nmfx_precision must be ..." goes out without the call's name in front
+    else:
+        try:
+            _precision(cfg, fn)
+        except ValueError as e:
+            raise ValueError(str(e) if fn in str(e) else "%s: %s" % (fn, e)) from None
+    if cfg.get("nmfx_gpus", None) is not None or cfg.get("nmfx_multi_backend", None) is not None:
+        raise ValueError("%s runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported" % fn)
+    if not _is_cell(Vs) or len(Vs) == 0:
+        raise ValueError("%s: Vs must be a non-empty list of matrices" % fn)
+    Vs = [np.asarray(v) for v in Vs]
+    B = len(Vs)
+    for b, v in enumerate(Vs):
+        if v.ndim != 2:
+            raise ValueError("%s: Vs[%d] must be a matrix" % (fn, b))
+        if v.shape[0] != Vs[0].shape[0]:
+            raise ValueError("%s: Vs[%d] has %d rows, Vs[0] has %d: the problems of a batch share their rows" % (fn, b, v.shape[0], Vs[0].shape[0]))
+        if v.shape[1] < 1 or v.shape[0] < 1:
+            raise ValueError("%s: Vs[%d] is empty" % (fn, b))
+    m = Vs[0].shape[0]
+    ns = [v.shape[1] for v in Vs]
+    if weighted and (not _is_cell(Ms) or len(Ms) != B):
+        raise ValueError("%s: Ms must be a list of %d weight matrices, one per problem" % (fn, B))
+    if _is_cell(num_basis_elems) or np.ndim(num_basis_elems) != 0:
+        raise ValueError("%s: num_basis_elems must be one positive integer (the batch has one source)" % fn)
+    K = int(num_basis_elems)
+    if K != num_basis_elems or K <= 0:
+        raise ValueError("%s: num_basis_elems must be a positive integer" % fn)
+    T = 1
+    if conv:
+        if _is_cell(context_len) or np.ndim(context_len) != 0 or isinstance(context_len, bool) or int(context_len) != context_len or int(context_len) <= 0:
+            raise ValueError("%s: context_len must be a positive integer" % fn)
+        T = int(context_len)
+        for b, n in enumerate(ns):
+            if n < T - 1:      # cnmf.m:188: [zeros(K, t-1) H(:, 1:n-t+1)] has the wrong width there and MATLAB errors
+                raise ValueError("%s: Vs[%d] has n_b = %d columns, fewer than T - 1 with T = %d: cnmf.m:188 has no H_shifted there" % (fn, b, n, T))
+        if K * T > 256:        # the convolutive calls refuse the product in Python
+            raise ValueError("%s: num_basis_elems * context_len = %d, at most 256 is supported" % (fn, K * T))
+    elif fn != "nmf_batch" and K > 256:     # wnmf_batch refuses K in Python; nmf_batch alone leaves K > 256 to the library
+        raise ValueError("%s: num_basis_elems = %d, at most 256 is supported" % (fn, K))
+    div = cfg.get("divergence", "euclidean")                       # nmf.m:250-252, cnmf.m:283-285
+    if (fn != "nmf_batch" and not isinstance(div, str)) or div not in _DIV_BATCH:     # nmf_batch only: no isinstance guard (an unhashable value is a TypeError there)
+        raise ValueError("%s has the euclidean and kl divergences only; got %r" % (fn, div))
+    dt = np.float32 if all(v.dtype == np.float32 for v in Vs) else np.float64
+    if weighted:               # after dt (the weights travel in it), before the inits
+        Ms = [_weights(fn, M, Vs[b].shape, dt, "Ms[%d]" % b, "Vs[%d]" % b) for b, M in enumerate(Ms)]
+    Hi, Wi = cfg.get("H_init", None), cfg.get("W_init", None)
+    if not _isempty(Hi):
+        if not _is_cell(Hi) or len(Hi) != B:
+            raise ValueError("%s: H_init must be a list of %d matrices" % (fn, B))
+        Hi = [np.asarray(h) for h in Hi]
+        for b, h in enumerate(Hi):
+            if h.shape != (K, ns[b]):
+                raise ValueError("%s: H_init[%d] must be %d-by-%d" % (fn, b, K, ns[b]))
+    else:
+        Hi = None
+    if not _isempty(Wi):
+        # the plain calls speak of an m-by-K matrix and take nothing else; the convolutive ones of an m-by-K-by-T tensor, with m-by-K allowed at T == 1
+        wform = ("%d-by-%d-by-%d" % (m, K, T), "tensor") if conv else ("%d-by-%d" % (m, K), "matrix")
+        if _is_cell(Wi):
+            if len(Wi) != B:
+                raise ValueError("%s: W_init must be one %s %s or a list of %d of them" % (fn, wform[0], wform[1], B))
+            Wi = [np.asarray(w) for w in Wi]
+        else:
+            Wi = [np.asarray(Wi)] * B
+        for b, w in enumerate(Wi):
+            if not ((conv and w.shape == (m, K, T)) or (T == 1 and w.shape == (m, K))):
+                raise ValueError("%s: W_init%s must be %s" % (fn, "[%d]" % b if _is_cell(cfg["W_init"]) else "", wform[0]))
+    else:
+        Wi = None
+    nonneg = lambda x: max(float(x), 0.0)
+    lw = _per_source(cfg, "W_sparsity", 1, 0.0, nonneg, "sparsity levels")      # nmf.m:312-401, cnmf.m:347-436, one source
+    lh = _per_source(cfg, "H_sparsity", 1, 0.0, nonneg, "sparsity levels")
+    fw = _per_source(cfg, "W_fixed", 1, False, bool, "update switches")
+    fh = _per_source(cfg, "H_fixed", 1, False, bool, "update switches")
+    maxiter = cfg.get("maxiter", None)
+    maxiter = 100 if maxiter is None or maxiter <= 0 else int(maxiter)          # nmf.m:404-406, cnmf.m:439-441
+    tol = cfg.get("tolerance", None)
+    tol = 1e-3 if tol is None or tol <= 0 else float(tol)                       # nmf.m:409-411, cnmf.m:444-446
+    rng = _rng(cfg)
+    off = np.zeros(B + 1, dtype=np.int64)
+    off[1:] = np.cumsum(ns)
+    N = int(off[B])
+    V_all = np.empty((m, N), order="F", dtype=dt)
+    M_all = np.empty((m, N), order="F", dtype=dt) if weighted else None
+    H_all = np.empty((K, N), order="F", dtype=dt)
+    W_all = np.empty((m, K, T, B), order="F", dtype=dt)     # (the plain calls' m-by-K-by-B is this with T = 1)
+    for b in range(B):
+        lo, hi = off[b], off[b + 1]
+        with np.errstate(**(dict(invalid="ignore", over="ignore") if weighted else {})):     # weighted only: what lies under a zero weight is carried along, never looked at
+            V_all[:, lo:hi] = Vs[b]
+        if weighted:
+            M_all[:, lo:hi] = Ms[b]
+        H_all[:, lo:hi] = Hi[b] if Hi is not None else np.fmax(rng.rand(K, ns[b]), EPS)     # nmf.m:277, cnmf.m:312
+        if Wi is not None:
+            W_all[:, :, :, b] = Wi[b].reshape(m, K, T)
+        elif conv:                 # cnmf.m:331-335, at T == 1 too: the draw follows the family
+            w = rng.rand(m, K, T)
+            W_all[:, :, :, b] = w / (np.sqrt(np.sum(w ** 2, axis=(0, 2))) / T)[None, :, None]
+        else:                      # nmf.m:298-299
+            w = np.fmax(rng.rand(m, K), EPS)
+            W_all[:, :, 0, b] = w * (1.0 / np.sqrt(np.sum(w ** 2, axis=0)))[None, :]
+    Wout = np.zeros((m, K, T, B), order="F", dtype=dt)
+    Hout = np.zeros((K, N), order="F", dtype=dt)
+    cost = np.zeros((maxiter, B), order="F")
+    lens = np.zeros(B, dtype=np.int32)
+    lw, lh = np.asarray(lw, dtype=np.float64), np.asarray(lh, dtype=np.float64)
+    fw, fh = np.asarray(fw, dtype=np.uint8), np.asarray(fh, dtype=np.uint8)
+    p = _lib.Problem()
+    p.m, p.n, p.K_total, p.T, p.dtype = m, N, K, T, (_lib.F32 if dt == np.float32 else _lib.F64)
+    p.V, p.W_init, p.H_init = _fptr(V_all), _fptr(W_all), _fptr(H_all)
+    p.divergence, p.alpha, p.beta = _DIV_BATCH[div], 1.0, 1.0
+    p.num_sources, p.K_s = 1, None
+    p.W_sparsity, p.H_sparsity, p.W_fixed, p.H_fixed = _fptr(lw), _fptr(lh), _fptr(fw), _fptr(fh)
+    p.maxiter = maxiter
+    p.tolerance = -1.0 if cfg.get("nmfx_disable_stop", False) else tol
+    p.device = int(device)
+    r = _lib.Result()
+    r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
+    entry = getattr(_lib.load(), "nmfx_" + fn)
+    _lib.check(entry(C.byref(p), *((_fptr(M_all),) if weighted else ()), B, _fptr(off), C.byref(r), _fptr(lens)))
+    # W[b] is m-by-K at T == 1 (rand(m,K,1) is a matrix in MATLAB; the plain calls have no other form)
+    return ([np.array(Wout[:, :, 0, b] if T == 1 else Wout[:, :, :, b]) for b in range(B)], [np.array(Hout[:, off[b]:off[b + 1]]) for b in range(B)],
+            [cost[: lens[b], b].copy() for b in range(B)])
+
+
 def nmf_batch(Vs, num_basis_elems, config=None, device=0):
     """W, H, cost = nmf_batch(Vs, num_basis_elems, config): B independent nmf problems (nmf.m:1) in one call -- three lists of length B, entry b being what
     nmf(Vs[b], num_basis_elems, config_b) returns: W[b] m-by-K, H[b] K-by-n_b, cost[b] trimmed by that problem's own stop rule.
@@ -381,99 +514,7 @@ def nmf_batch(Vs, num_basis_elems, config=None, device=0):
 
     Refused with ValueError: an empty batch, a Vs[b] that is not a matrix, differing row counts, inits of the wrong count or shape, the 'is' / 'ab'
     divergences (and unknown ones), nmfx_gpus, nmfx_multi_backend and nmfx_precision='float64'.  nmfx_path is ignored (there is one path)."""
-    cfg = dict(config) if config else {}
-    _precision(cfg, "nmf_batch")
-    if cfg.get("nmfx_gpus", None) is not None or cfg.get("nmfx_multi_backend", None) is not None:
-        raise ValueError("nmf_batch runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported")
-    if not _is_cell(Vs) or len(Vs) == 0:
-        raise ValueError("nmf_batch: Vs must be a non-empty list of matrices")
-    Vs = [np.asarray(v) for v in Vs]
-    B = len(Vs)
-    for b, v in enumerate(Vs):
-        if v.ndim != 2:
-            raise ValueError("nmf_batch: Vs[%d] must be a matrix" % b)
-        if v.shape[0] != Vs[0].shape[0]:
-            raise ValueError("nmf_batch: Vs[%d] has %d rows, Vs[0] has %d: the problems of a batch share their rows" % (b, v.shape[0], Vs[0].shape[0]))
-        if v.shape[1] < 1 or v.shape[0] < 1:
-            raise ValueError("nmf_batch: Vs[%d] is empty" % b)
-    if _is_cell(num_basis_elems) or np.ndim(num_basis_elems) != 0:
-        raise ValueError("nmf_batch: num_basis_elems must be one positive integer (the batch has one source)")
-    K = int(num_basis_elems)
-    if K != num_basis_elems or K <= 0:
-        raise ValueError("nmf_batch: num_basis_elems must be a positive integer")
-    div = cfg.get("divergence", "euclidean")                       # nmf.m:250-252
-    if div not in _DIV_BATCH:
-        raise ValueError("nmf_batch has the euclidean and kl divergences only; got %r" % (div,))
-    dt = np.float32 if all(v.dtype == np.float32 for v in Vs) else np.float64
-    m = Vs[0].shape[0]
-    ns = [v.shape[1] for v in Vs]
-    Hi, Wi = cfg.get("H_init", None), cfg.get("W_init", None)
-    if not _isempty(Hi):
-        if not _is_cell(Hi) or len(Hi) != B:
-            raise ValueError("nmf_batch: H_init must be a list of %d matrices" % B)
-        Hi = [np.asarray(h) for h in Hi]
-        for b, h in enumerate(Hi):
-            if h.shape != (K, ns[b]):
-                raise ValueError("nmf_batch: H_init[%d] must be %d-by-%d" % (b, K, ns[b]))
-    else:
-        Hi = None
-    if not _isempty(Wi):
-        if _is_cell(Wi):
-            if len(Wi) != B:
-                raise ValueError("nmf_batch: W_init must be one %d-by-%d matrix or a list of %d of them" % (m, K, B))
-            Wi = [np.asarray(w) for w in Wi]
-        else:
-            Wi = [np.asarray(Wi)] * B
-        for b, w in enumerate(Wi):
-            if w.shape != (m, K):
-                raise ValueError("nmf_batch: W_init%s must be %d-by-%d" % ("[%d]" % b if _is_cell(cfg["W_init"]) else "", m, K))
-    else:
-        Wi = None
-    nonneg = lambda x: max(float(x), 0.0)
-    lw = _per_source(cfg, "W_sparsity", 1, 0.0, nonneg, "sparsity levels")      # nmf.m:312-401, one source
-    lh = _per_source(cfg, "H_sparsity", 1, 0.0, nonneg, "sparsity levels")
-    fw = _per_source(cfg, "W_fixed", 1, False, bool, "update switches")
-    fh = _per_source(cfg, "H_fixed", 1, False, bool, "update switches")
-    maxiter = cfg.get("maxiter", None)
-    maxiter = 100 if maxiter is None or maxiter <= 0 else int(maxiter)          # nmf.m:404-406
-    tol = cfg.get("tolerance", None)
-    tol = 1e-3 if tol is None or tol <= 0 else float(tol)                       # nmf.m:409-411
-    rng = _rng(cfg)
-    off = np.zeros(B + 1, dtype=np.int64)
-    off[1:] = np.cumsum(ns)
-    N = int(off[B])
-    V_all = np.empty((m, N), order="F", dtype=dt)
-    H_all = np.empty((K, N), order="F", dtype=dt)
-    W_all = np.empty((m, K, B), order="F", dtype=dt)
-    for b in range(B):
-        lo, hi = off[b], off[b + 1]
-        V_all[:, lo:hi] = Vs[b]
-        H_all[:, lo:hi] = Hi[b] if Hi is not None else np.fmax(rng.rand(K, ns[b]), EPS)     # nmf.m:277
-        if Wi is not None:
-            W_all[:, :, b] = Wi[b]
-        else:                                                                              # nmf.m:298-299
-            w = np.fmax(rng.rand(m, K), EPS)
-            W_all[:, :, b] = w * (1.0 / np.sqrt(np.sum(w ** 2, axis=0)))[None, :]
-    Wout = np.zeros((m, K, B), order="F", dtype=dt)
-    Hout = np.zeros((K, N), order="F", dtype=dt)
-    cost = np.zeros((maxiter, B), order="F")
-    lens = np.zeros(B, dtype=np.int32)
-    lw, lh = np.asarray(lw, dtype=np.float64), np.asarray(lh, dtype=np.float64)
-    fw, fh = np.asarray(fw, dtype=np.uint8), np.asarray(fh, dtype=np.uint8)
-    p = _lib.Problem()
-    p.m, p.n, p.K_total, p.T, p.dtype = m, N, K, 1, (_lib.F32 if dt == np.float32 else _lib.F64)
-    p.V, p.W_init, p.H_init = _fptr(V_all), _fptr(W_all), _fptr(H_all)
-    p.divergence, p.alpha, p.beta = _DIV_BATCH[div], 1.0, 1.0
-    p.num_sources, p.K_s = 1, None
-    p.W_sparsity, p.H_sparsity, p.W_fixed, p.H_fixed = _fptr(lw), _fptr(lh), _fptr(fw), _fptr(fh)
-    p.maxiter = maxiter
-    p.tolerance = -1.0 if cfg.get("nmfx_disable_stop", False) else tol
-    p.device = int(device)
-    r = _lib.Result()
-    r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
-    _lib.check(_lib.load().nmfx_nmf_batch(C.byref(p), B, _fptr(off), C.byref(r), _fptr(lens)))
-    return ([np.array(Wout[:, :, b]) for b in range(B)], [np.array(Hout[:, off[b]:off[b + 1]]) for b in range(B)],
-            [cost[: lens[b], b].copy() for b in range(B)])
+    return _batch("nmf_batch", Vs, None, num_basis_elems, None, config, device)
 
 
 def wnmf_batch(Vs, Ms, num_basis_elems, config=None, device=0):
@@ -493,110 +534,7 @@ def wnmf_batch(Vs, Ms, num_basis_elems, config=None, device=0):
 
     Refused with ValueError: everything nmf_batch refuses (the 'is' / 'ab' divergences included), Ms that is not a list of B arrays, a Ms[b] of another
     shape than Vs[b] or of a non-real kind, and a weight that is negative or not finite.  nmfx_path is ignored (there is one path)."""
-    cfg = dict(config) if config else {}
-    try:
-        _precision(cfg, "wnmf_batch")
-    except ValueError as e:
-        raise ValueError(str(e) if "wnmf_batch" in str(e) else "wnmf_batch: %s" % e) from None
-    if cfg.get("nmfx_gpus", None) is not None or cfg.get("nmfx_multi_backend", None) is not None:
-        raise ValueError("wnmf_batch runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported")
-    if not _is_cell(Vs) or len(Vs) == 0:
-        raise ValueError("wnmf_batch: Vs must be a non-empty list of matrices")
-    Vs = [np.asarray(v) for v in Vs]
-    B = len(Vs)
-    for b, v in enumerate(Vs):
-        if v.ndim != 2:
-            raise ValueError("wnmf_batch: Vs[%d] must be a matrix" % b)
-        if v.shape[0] != Vs[0].shape[0]:
-            raise ValueError("wnmf_batch: Vs[%d] has %d rows, Vs[0] has %d: the problems of a batch share their rows" % (b, v.shape[0], Vs[0].shape[0]))
-        if v.shape[1] < 1 or v.shape[0] < 1:
-            raise ValueError("wnmf_batch: Vs[%d] is empty" % b)
-    if not _is_cell(Ms) or len(Ms) != B:
-        raise ValueError("wnmf_batch: Ms must be a list of %d weight matrices, one per problem" % B)
-    if _is_cell(num_basis_elems) or np.ndim(num_basis_elems) != 0:
-        raise ValueError("wnmf_batch: num_basis_elems must be one positive integer (the batch has one source)")
-    K = int(num_basis_elems)
-    if K != num_basis_elems or K <= 0:
-        raise ValueError("wnmf_batch: num_basis_elems must be a positive integer")
-    if K > 256:
-        raise ValueError("wnmf_batch: num_basis_elems = %d, at most 256 is supported" % K)
-    div = cfg.get("divergence", "euclidean")                       # nmf.m:250-252
-    if not isinstance(div, str) or div not in _DIV_BATCH:
-        raise ValueError("wnmf_batch has the euclidean and kl divergences only; got %r" % (div,))
-    dt = np.float32 if all(v.dtype == np.float32 for v in Vs) else np.float64
-    Ms = [_weights("wnmf_batch", M, Vs[b].shape, dt, "Ms[%d]" % b, "Vs[%d]" % b) for b, M in enumerate(Ms)]
-    m = Vs[0].shape[0]
-    ns = [v.shape[1] for v in Vs]
-    Hi, Wi = cfg.get("H_init", None), cfg.get("W_init", None)
-    if not _isempty(Hi):
-        if not _is_cell(Hi) or len(Hi) != B:
-            raise ValueError("wnmf_batch: H_init must be a list of %d matrices" % B)
-        Hi = [np.asarray(h) for h in Hi]
-        for b, h in enumerate(Hi):
-            if h.shape != (K, ns[b]):
-                raise ValueError("wnmf_batch: H_init[%d] must be %d-by-%d" % (b, K, ns[b]))
-    else:
-        Hi = None
-    if not _isempty(Wi):
-        if _is_cell(Wi):
-            if len(Wi) != B:
-                raise ValueError("wnmf_batch: W_init must be one %d-by-%d matrix or a list of %d of them" % (m, K, B))
-            Wi = [np.asarray(w) for w in Wi]
-        else:
-            Wi = [np.asarray(Wi)] * B
-        for b, w in enumerate(Wi):
-            if w.shape != (m, K):
-                raise ValueError("wnmf_batch: W_init%s must be %d-by-%d" % ("[%d]" % b if _is_cell(cfg["W_init"]) else "", m, K))
-    else:
-        Wi = None
-    nonneg = lambda x: max(float(x), 0.0)
-    lw = _per_source(cfg, "W_sparsity", 1, 0.0, nonneg, "sparsity levels")      # nmf.m:312-401, one source
-    lh = _per_source(cfg, "H_sparsity", 1, 0.0, nonneg, "sparsity levels")
-    fw = _per_source(cfg, "W_fixed", 1, False, bool, "update switches")
-    fh = _per_source(cfg, "H_fixed", 1, False, bool, "update switches")
-    maxiter = cfg.get("maxiter", None)
-    maxiter = 100 if maxiter is None or maxiter <= 0 else int(maxiter)          # nmf.m:404-406
-    tol = cfg.get("tolerance", None)
-    tol = 1e-3 if tol is None or tol <= 0 else float(tol)                       # nmf.m:409-411
-    rng = _rng(cfg)
-    off = np.zeros(B + 1, dtype=np.int64)
-    off[1:] = np.cumsum(ns)
-    N = int(off[B])
-    V_all = np.empty((m, N), order="F", dtype=dt)
-    M_all = np.empty((m, N), order="F", dtype=dt)
-    H_all = np.empty((K, N), order="F", dtype=dt)
-    W_all = np.empty((m, K, B), order="F", dtype=dt)
-    for b in range(B):
-        lo, hi = off[b], off[b + 1]
-        with np.errstate(invalid="ignore", over="ignore"):      # (what lies under a zero weight is carried along, never looked at)
-            V_all[:, lo:hi] = Vs[b]
-        M_all[:, lo:hi] = Ms[b]
-        H_all[:, lo:hi] = Hi[b] if Hi is not None else np.fmax(rng.rand(K, ns[b]), EPS)     # nmf.m:277
-        if Wi is not None:
-            W_all[:, :, b] = Wi[b]
-        else:                                                                              # nmf.m:298-299
-            w = np.fmax(rng.rand(m, K), EPS)
-            W_all[:, :, b] = w * (1.0 / np.sqrt(np.sum(w ** 2, axis=0)))[None, :]
-    Wout = np.zeros((m, K, B), order="F", dtype=dt)
-    Hout = np.zeros((K, N), order="F", dtype=dt)
-    cost = np.zeros((maxiter, B), order="F")
-    lens = np.zeros(B, dtype=np.int32)
-    lw, lh = np.asarray(lw, dtype=np.float64), np.asarray(lh, dtype=np.float64)
-    fw, fh = np.asarray(fw, dtype=np.uint8), np.asarray(fh, dtype=np.uint8)
-    p = _lib.Problem()
-    p.m, p.n, p.K_total, p.T, p.dtype = m, N, K, 1, (_lib.F32 if dt == np.float32 else _lib.F64)
-    p.V, p.W_init, p.H_init = _fptr(V_all), _fptr(W_all), _fptr(H_all)
-    p.divergence, p.alpha, p.beta = _DIV_BATCH[div], 1.0, 1.0
-    p.num_sources, p.K_s = 1, None
-    p.W_sparsity, p.H_sparsity, p.W_fixed, p.H_fixed = _fptr(lw), _fptr(lh), _fptr(fw), _fptr(fh)
-    p.maxiter = maxiter
-    p.tolerance = -1.0 if cfg.get("nmfx_disable_stop", False) else tol
-    p.device = int(device)
-    r = _lib.Result()
-    r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
-    _lib.check(_lib.load().nmfx_wnmf_batch(C.byref(p), _fptr(M_all), B, _fptr(off), C.byref(r), _fptr(lens)))
-    return ([np.array(Wout[:, :, b]) for b in range(B)], [np.array(Hout[:, off[b]:off[b + 1]]) for b in range(B)],
-            [cost[: lens[b], b].copy() for b in range(B)])
+    return _batch("wnmf_batch", Vs, Ms, num_basis_elems, None, config, device)
 
 
 def cnmf(V, num_basis_elems, context_len, config=None, device=0):
@@ -635,110 +573,7 @@ def cnmf_batch(Vs, num_basis_elems, context_len, config=None, device=0):
 
     Refused with ValueError: an empty batch, a Vs[b] that is not a non-empty matrix, differing row counts, n_b < T - 1, K * T > 256, inits of the wrong count
     or shape, every divergence but euclidean and kl, nmfx_gpus, nmfx_multi_backend and nmfx_precision='float64'.  nmfx_path is ignored (there is one path)."""
-    cfg = dict(config) if config else {}
-    try:
-        _precision(cfg, "cnmf_batch")
-    except ValueError as e:
-        raise ValueError(str(e) if "cnmf_batch" in str(e) else "cnmf_batch: %s" % e) from None
-    if cfg.get("nmfx_gpus", None) is not None or cfg.get("nmfx_multi_backend", None) is not None:
-        raise ValueError("cnmf_batch runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported")
-    if not _is_cell(Vs) or len(Vs) == 0:
-        raise ValueError("cnmf_batch: Vs must be a non-empty list of matrices")
-    Vs = [np.asarray(v) for v in Vs]
-    B = len(Vs)
-    for b, v in enumerate(Vs):
-        if v.ndim != 2:
-            raise ValueError("cnmf_batch: Vs[%d] must be a matrix" % b)
-        if v.shape[0] != Vs[0].shape[0]:
-            raise ValueError("cnmf_batch: Vs[%d] has %d rows, Vs[0] has %d: the problems of a batch share their rows" % (b, v.shape[0], Vs[0].shape[0]))
-        if v.shape[1] < 1 or v.shape[0] < 1:
-            raise ValueError("cnmf_batch: Vs[%d] is empty" % b)
-    if _is_cell(num_basis_elems) or np.ndim(num_basis_elems) != 0:
-        raise ValueError("cnmf_batch: num_basis_elems must be one positive integer (the batch has one source)")
-    K = int(num_basis_elems)
-    if K != num_basis_elems or K <= 0:
-        raise ValueError("cnmf_batch: num_basis_elems must be a positive integer")
-    if _is_cell(context_len) or np.ndim(context_len) != 0 or isinstance(context_len, bool) or int(context_len) != context_len or int(context_len) <= 0:
-        raise ValueError("cnmf_batch: context_len must be a positive integer")
-    T = int(context_len)
-    m = Vs[0].shape[0]
-    ns = [v.shape[1] for v in Vs]
-    for b, n in enumerate(ns):
-        if n < T - 1:      # cnmf.m:188: [zeros(K, t-1) H(:, 1:n-t+1)] has the wrong width there and MATLAB errors
-            raise ValueError("cnmf_batch: Vs[%d] has n_b = %d columns, fewer than T - 1 with T = %d: cnmf.m:188 has no H_shifted there" % (b, n, T))
-    if K * T > 256:
-        raise ValueError("cnmf_batch: num_basis_elems * context_len = %d, at most 256 is supported" % (K * T))
-    div = cfg.get("divergence", "euclidean")                       # cnmf.m:283-285
-    if not isinstance(div, str) or div not in _DIV_BATCH:
-        raise ValueError("cnmf_batch has the euclidean and kl divergences only; got %r" % (div,))
-    dt = np.float32 if all(v.dtype == np.float32 for v in Vs) else np.float64
-    Hi, Wi = cfg.get("H_init", None), cfg.get("W_init", None)
-    if not _isempty(Hi):
-        if not _is_cell(Hi) or len(Hi) != B:
-            raise ValueError("cnmf_batch: H_init must be a list of %d matrices" % B)
-        Hi = [np.asarray(h) for h in Hi]
-        for b, h in enumerate(Hi):
-            if h.shape != (K, ns[b]):
-                raise ValueError("cnmf_batch: H_init[%d] must be %d-by-%d" % (b, K, ns[b]))
-    else:
-        Hi = None
-    if not _isempty(Wi):
-        if _is_cell(Wi):
-            if len(Wi) != B:
-                raise ValueError("cnmf_batch: W_init must be one %d-by-%d-by-%d tensor or a list of %d of them" % (m, K, T, B))
-            Wi = [np.asarray(w) for w in Wi]
-        else:
-            Wi = [np.asarray(Wi)] * B
-        for b, w in enumerate(Wi):
-            if w.shape != (m, K, T) and not (T == 1 and w.shape == (m, K)):
-                raise ValueError("cnmf_batch: W_init%s must be %d-by-%d-by-%d" % ("[%d]" % b if _is_cell(cfg["W_init"]) else "", m, K, T))
-    else:
-        Wi = None
-    nonneg = lambda x: max(float(x), 0.0)
-    lw = _per_source(cfg, "W_sparsity", 1, 0.0, nonneg, "sparsity levels")      # cnmf.m:347-436, one source
-    lh = _per_source(cfg, "H_sparsity", 1, 0.0, nonneg, "sparsity levels")
-    fw = _per_source(cfg, "W_fixed", 1, False, bool, "update switches")
-    fh = _per_source(cfg, "H_fixed", 1, False, bool, "update switches")
-    maxiter = cfg.get("maxiter", None)
-    maxiter = 100 if maxiter is None or maxiter <= 0 else int(maxiter)          # cnmf.m:439-441
-    tol = cfg.get("tolerance", None)
-    tol = 1e-3 if tol is None or tol <= 0 else float(tol)                       # cnmf.m:444-446
-    rng = _rng(cfg)
-    off = np.zeros(B + 1, dtype=np.int64)
-    off[1:] = np.cumsum(ns)
-    N = int(off[B])
-    V_all = np.empty((m, N), order="F", dtype=dt)
-    H_all = np.empty((K, N), order="F", dtype=dt)
-    W_all = np.empty((m, K, T, B), order="F", dtype=dt)
-    for b in range(B):
-        lo, hi = off[b], off[b + 1]
-        V_all[:, lo:hi] = Vs[b]
-        H_all[:, lo:hi] = Hi[b] if Hi is not None else np.fmax(rng.rand(K, ns[b]), EPS)     # cnmf.m:312
-        if Wi is not None:
-            W_all[:, :, :, b] = Wi[b].reshape(m, K, T)
-        else:                                                                              # cnmf.m:331-335
-            w = rng.rand(m, K, T)
-            W_all[:, :, :, b] = w / (np.sqrt(np.sum(w ** 2, axis=(0, 2))) / T)[None, :, None]
-    Wout = np.zeros((m, K, T, B), order="F", dtype=dt)
-    Hout = np.zeros((K, N), order="F", dtype=dt)
-    cost = np.zeros((maxiter, B), order="F")
-    lens = np.zeros(B, dtype=np.int32)
-    lw, lh = np.asarray(lw, dtype=np.float64), np.asarray(lh, dtype=np.float64)
-    fw, fh = np.asarray(fw, dtype=np.uint8), np.asarray(fh, dtype=np.uint8)
-    p = _lib.Problem()
-    p.m, p.n, p.K_total, p.T, p.dtype = m, N, K, T, (_lib.F32 if dt == np.float32 else _lib.F64)
-    p.V, p.W_init, p.H_init = _fptr(V_all), _fptr(W_all), _fptr(H_all)
-    p.divergence, p.alpha, p.beta = _DIV_BATCH[div], 1.0, 1.0
-    p.num_sources, p.K_s = 1, None
-    p.W_sparsity, p.H_sparsity, p.W_fixed, p.H_fixed = _fptr(lw), _fptr(lh), _fptr(fw), _fptr(fh)
-    p.maxiter = maxiter
-    p.tolerance = -1.0 if cfg.get("nmfx_disable_stop", False) else tol
-    p.device = int(device)
-    r = _lib.Result()
-    r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
-    _lib.check(_lib.load().nmfx_cnmf_batch(C.byref(p), B, _fptr(off), C.byref(r), _fptr(lens)))
-    return ([np.array(Wout[:, :, 0, b] if T == 1 else Wout[:, :, :, b]) for b in range(B)], [np.array(Hout[:, off[b]:off[b + 1]]) for b in range(B)],
-            [cost[: lens[b], b].copy() for b in range(B)])
+    return _batch("cnmf_batch", Vs, None, num_basis_elems, context_len, config, device)
 
 
 def wcnmf_batch(Vs, Ms, num_basis_elems, context_len, config=None, device=0):
@@ -761,116 +596,7 @@ def wcnmf_batch(Vs, Ms, num_basis_elems, context_len, config=None, device=0):
     Refused with ValueError: everything cnmf_batch refuses (the 'is' / 'ab' divergences, n_b < T - 1 and K * T > 256 included), Ms that is not a list of B
     arrays, a Ms[b] of another shape than Vs[b] or of a non-real kind, and a weight that is negative or not finite.  nmfx_path is ignored (there is one
     path)."""
-    cfg = dict(config) if config else {}
-    try:
-        _precision(cfg, "wcnmf_batch")
-    except ValueError as e:
-        raise ValueError(str(e) if "wcnmf_batch" in str(e) else "wcnmf_batch: %s" % e) from None
-    if cfg.get("nmfx_gpus", None) is not None or cfg.get("nmfx_multi_backend", None) is not None:
-        raise ValueError("wcnmf_batch runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported")
-    if not _is_cell(Vs) or len(Vs) == 0:
-        raise ValueError("wcnmf_batch: Vs must be a non-empty list of matrices")
-    Vs = [np.asarray(v) for v in Vs]
-    B = len(Vs)
-    for b, v in enumerate(Vs):
-        if v.ndim != 2:
-            raise ValueError("wcnmf_batch: Vs[%d] must be a matrix" % b)
-        if v.shape[0] != Vs[0].shape[0]:
-            raise ValueError("wcnmf_batch: Vs[%d] has %d rows, Vs[0] has %d: the problems of a batch share their rows" % (b, v.shape[0], Vs[0].shape[0]))
-        if v.shape[1] < 1 or v.shape[0] < 1:
-            raise ValueError("wcnmf_batch: Vs[%d] is empty" % b)
-    if not _is_cell(Ms) or len(Ms) != B:
-        raise ValueError("wcnmf_batch: Ms must be a list of %d weight matrices, one per problem" % B)
-    if _is_cell(num_basis_elems) or np.ndim(num_basis_elems) != 0:
-        raise ValueError("wcnmf_batch: num_basis_elems must be one positive integer (the batch has one source)")
-    K = int(num_basis_elems)
-    if K != num_basis_elems or K <= 0:
-        raise ValueError("wcnmf_batch: num_basis_elems must be a positive integer")
-    if _is_cell(context_len) or np.ndim(context_len) != 0 or isinstance(context_len, bool) or int(context_len) != context_len or int(context_len) <= 0:
-        raise ValueError("wcnmf_batch: context_len must be a positive integer")
-    T = int(context_len)
-    m = Vs[0].shape[0]
-    ns = [v.shape[1] for v in Vs]
-    for b, n in enumerate(ns):
-        if n < T - 1:      # cnmf.m:188: [zeros(K, t-1) H(:, 1:n-t+1)] has the wrong width there and MATLAB errors
-            raise ValueError("wcnmf_batch: Vs[%d] has n_b = %d columns, fewer than T - 1 with T = %d: cnmf.m:188 has no H_shifted there" % (b, n, T))
-    if K * T > 256:
-        raise ValueError("wcnmf_batch: num_basis_elems * context_len = %d, at most 256 is supported" % (K * T))
-    div = cfg.get("divergence", "euclidean")                       # cnmf.m:283-285
-    if not isinstance(div, str) or div not in _DIV_BATCH:
-        raise ValueError("wcnmf_batch has the euclidean and kl divergences only; got %r" % (div,))
-    dt = np.float32 if all(v.dtype == np.float32 for v in Vs) else np.float64
-    Ms = [_weights("wcnmf_batch", M, Vs[b].shape, dt, "Ms[%d]" % b, "Vs[%d]" % b) for b, M in enumerate(Ms)]
-    Hi, Wi = cfg.get("H_init", None), cfg.get("W_init", None)
-    if not _isempty(Hi):
-        if not _is_cell(Hi) or len(Hi) != B:
-            raise ValueError("wcnmf_batch: H_init must be a list of %d matrices" % B)
-        Hi = [np.asarray(h) for h in Hi]
-        for b, h in enumerate(Hi):
-            if h.shape != (K, ns[b]):
-                raise ValueError("wcnmf_batch: H_init[%d] must be %d-by-%d" % (b, K, ns[b]))
-    else:
-        Hi = None
-    if not _isempty(Wi):
-        if _is_cell(Wi):
-            if len(Wi) != B:
-                raise ValueError("wcnmf_batch: W_init must be one %d-by-%d-by-%d tensor or a list of %d of them" % (m, K, T, B))
-            Wi = [np.asarray(w) for w in Wi]
-        else:
-            Wi = [np.asarray(Wi)] * B
-        for b, w in enumerate(Wi):
-            if w.shape != (m, K, T) and not (T == 1 and w.shape == (m, K)):
-                raise ValueError("wcnmf_batch: W_init%s must be %d-by-%d-by-%d" % ("[%d]" % b if _is_cell(cfg["W_init"]) else "", m, K, T))
-    else:
-        Wi = None
-    nonneg = lambda x: max(float(x), 0.0)
-    lw = _per_source(cfg, "W_sparsity", 1, 0.0, nonneg, "sparsity levels")      # cnmf.m:347-436, one source
-    lh = _per_source(cfg, "H_sparsity", 1, 0.0, nonneg, "sparsity levels")
-    fw = _per_source(cfg, "W_fixed", 1, False, bool, "update switches")
-    fh = _per_source(cfg, "H_fixed", 1, False, bool, "update switches")
-    maxiter = cfg.get("maxiter", None)
-    maxiter = 100 if maxiter is None or maxiter <= 0 else int(maxiter)          # cnmf.m:439-441
-    tol = cfg.get("tolerance", None)
-    tol = 1e-3 if tol is None or tol <= 0 else float(tol)                       # cnmf.m:444-446
-    rng = _rng(cfg)
-    off = np.zeros(B + 1, dtype=np.int64)
-    off[1:] = np.cumsum(ns)
-    N = int(off[B])
-    V_all = np.empty((m, N), order="F", dtype=dt)
-    M_all = np.empty((m, N), order="F", dtype=dt)
-    H_all = np.empty((K, N), order="F", dtype=dt)
-    W_all = np.empty((m, K, T, B), order="F", dtype=dt)
-    for b in range(B):
-        lo, hi = off[b], off[b + 1]
-        with np.errstate(invalid="ignore", over="ignore"):      # (what lies under a zero weight is carried along, never looked at)
-            V_all[:, lo:hi] = Vs[b]
-        M_all[:, lo:hi] = Ms[b]
-        H_all[:, lo:hi] = Hi[b] if Hi is not None else np.fmax(rng.rand(K, ns[b]), EPS)     # cnmf.m:312
-        if Wi is not None:
-            W_all[:, :, :, b] = Wi[b].reshape(m, K, T)
-        else:                                                                              # cnmf.m:331-335
-            w = rng.rand(m, K, T)
-            W_all[:, :, :, b] = w / (np.sqrt(np.sum(w ** 2, axis=(0, 2))) / T)[None, :, None]
-    Wout = np.zeros((m, K, T, B), order="F", dtype=dt)
-    Hout = np.zeros((K, N), order="F", dtype=dt)
-    cost = np.zeros((maxiter, B), order="F")
-    lens = np.zeros(B, dtype=np.int32)
-    lw, lh = np.asarray(lw, dtype=np.float64), np.asarray(lh, dtype=np.float64)
-    fw, fh = np.asarray(fw, dtype=np.uint8), np.asarray(fh, dtype=np.uint8)
-    p = _lib.Problem()
-    p.m, p.n, p.K_total, p.T, p.dtype = m, N, K, T, (_lib.F32 if dt == np.float32 else _lib.F64)
-    p.V, p.W_init, p.H_init = _fptr(V_all), _fptr(W_all), _fptr(H_all)
-    p.divergence, p.alpha, p.beta = _DIV_BATCH[div], 1.0, 1.0
-    p.num_sources, p.K_s = 1, None
-    p.W_sparsity, p.H_sparsity, p.W_fixed, p.H_fixed = _fptr(lw), _fptr(lh), _fptr(fw), _fptr(fh)
-    p.maxiter = maxiter
-    p.tolerance = -1.0 if cfg.get("nmfx_disable_stop", False) else tol
-    p.device = int(device)
-    r = _lib.Result()
-    r.W, r.H, r.cost = _fptr(Wout), _fptr(Hout), _fptr(cost)
-    _lib.check(_lib.load().nmfx_wcnmf_batch(C.byref(p), _fptr(M_all), B, _fptr(off), C.byref(r), _fptr(lens)))
-    return ([np.array(Wout[:, :, 0, b] if T == 1 else Wout[:, :, :, b]) for b in range(B)], [np.array(Hout[:, off[b]:off[b + 1]]) for b in range(B)],
-            [cost[: lens[b], b].copy() for b in range(B)])
+    return _batch("wcnmf_batch", Vs, Ms, num_basis_elems, context_len, config, device)
 
 
 def lnmf(V, num_basis_elems, config=None, device=0):

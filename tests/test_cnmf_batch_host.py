@@ -177,3 +177,17 @@ def test_c_abi_argument_errors():
     assert st == L.NMFX_ERR_UNSUPPORTED and "256" in msg
     st, msg = _raw(2, [0, 4, 10], 10, K=257, T=1)
     assert st == L.NMFX_ERR_UNSUPPORTED and "256" in msg
+
+
+def test_k_limit_is_refused_in_python(no_library):
+    """K * T > 256 never reaches the library, at T = 1 too and in the words of the product; K * T = 256 passes the check (it gets as far as loading
+    the library)"""
+    import nmf_toolbox_amd as A
+    Vs = [np.ones((16, 9)), np.ones((16, 7))]
+    for k, t in ((129, 2), (257, 1)):
+        with pytest.raises(ValueError) as e:
+            A.cnmf_batch(Vs, k, t, dict(seed=0))
+        assert str(e.value) == "cnmf_batch: num_basis_elems * context_len = %d, at most 256 is supported" % (k * t)
+    with pytest.raises(AssertionError) as e:
+        A.cnmf_batch(Vs, 128, 2, dict(seed=0))
+    assert "the library was loaded" in str(e.value)

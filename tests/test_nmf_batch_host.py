@@ -133,3 +133,20 @@ def test_c_abi_argument_errors():
     assert st == L.NMFX_ERR_UNSUPPORTED and "one GPU" in msg
     st, msg = _raw(2, [0, 4, 10], 10, K=257)
     assert st == L.NMFX_ERR_UNSUPPORTED and "256" in msg
+
+
+def test_what_only_nmf_batch_does(no_library):
+    """three things nmf_batch does differently from the other three batch calls, kept as they are: the nmfx_precision message goes out as _precision
+    words it, without the call's name in front; a divergence that cannot be hashed is not turned into a ValueError; and K > 256 is not refused in
+    Python -- the library refuses it (test_c_abi_argument_errors), so with the library taken away the call gets as far as loading it"""
+    import nmf_toolbox_amd as A
+    Vs = [p[0] for p in _three()]
+    for bad in ("half", 64, ""):
+        with pytest.raises(ValueError) as e:
+            A.nmf_batch(Vs, 3, dict(nmfx_precision=bad))
+        assert str(e.value) == "nmfx_precision must be 'float32' ('single') or 'float64' ('double'); got %r" % (bad,)
+    with pytest.raises(TypeError):
+        A.nmf_batch(Vs, 3, dict(divergence=["kl"]))
+    with pytest.raises(AssertionError) as e:
+        A.nmf_batch(Vs, 257, dict(seed=0))
+    assert "the library was loaded" in str(e.value)

@@ -441,3 +441,18 @@ def test_the_restatement_with_sparsity_meets_the_oracle():
         got = device_flow(Vs, Ms, W0s, H0s, Kc, Tc, div, iters, 0.1, 0.2)
         for b, (W, H, c) in enumerate(I.oracle(m, Kc, Tc, tuple(ns), div, iters, "weights", extra=tuple(sorted(extra.items())))):
             assert rel_fro(got[b][0], W) <= 1e-12 and rel_fro(got[b][1], H) <= 1e-12 and _cost_err(got[b][2], c, ns[b], Kc * Tc) <= 1e-12, (div, b)
+
+
+def test_k_limit_is_refused_in_python(no_library):
+    """K * T > 256 never reaches the library, at T = 1 too and in the words of the product; K * T = 256 passes the check (it gets as far as loading
+    the library)"""
+    import nmf_toolbox_amd as A
+    Vs = [np.ones((16, 9)), np.ones((16, 7))]
+    Ms = [np.ones_like(v) for v in Vs]
+    for k, t in ((129, 2), (257, 1)):
+        with pytest.raises(ValueError) as e:
+            A.wcnmf_batch(Vs, Ms, k, t, dict(seed=0))
+        assert str(e.value) == "wcnmf_batch: num_basis_elems * context_len = %d, at most 256 is supported" % (k * t)
+    with pytest.raises(AssertionError) as e:
+        A.wcnmf_batch(Vs, Ms, 128, 2, dict(seed=0))
+    assert "the library was loaded" in str(e.value)

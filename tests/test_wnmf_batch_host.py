@@ -255,3 +255,16 @@ def test_rounding_the_inputs_to_fp32_stays_a_tenth_below_the_contract():
             eC = max(eC, float(np.max(np.abs(c - c0) / (c0 if ns[b] > Kc else c0[0]))))
         print(div, eWH, eC)
         assert eWH <= 1e-6 and eC <= 1e-7
+
+
+def test_k_limit_is_refused_in_python(no_library):
+    """K > 256 never reaches the library, and K = 256 passes the check (it gets as far as loading the library)"""
+    import nmf_toolbox_amd as A
+    Vs = [np.ones((16, 9)), np.ones((16, 7))]
+    Ms = [np.ones_like(v) for v in Vs]
+    with pytest.raises(ValueError) as e:
+        A.wnmf_batch(Vs, Ms, 257, dict(seed=0))
+    assert str(e.value) == "wnmf_batch: num_basis_elems = 257, at most 256 is supported"
+    with pytest.raises(AssertionError) as e:
+        A.wnmf_batch(Vs, Ms, 256, dict(seed=0))
+    assert "the library was loaded" in str(e.value)
