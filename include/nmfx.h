@@ -318,6 +318,28 @@ nmfx_status nmfx_softmask_dev(void *stream, int64_t m, int64_t n, int32_t num_so
                               int32_t K, int32_t T, int32_t is_complex, int32_t layout /* 0 column-major, 1 row-major */,
                               const void *X_dev, int64_t ldx, const float *W_dev, const float *H_dev, double power, int32_t output,
                               void *Y_dev, int64_t ldy, int64_t y_slab /* elements between the outputs of consecutive sources */, int32_t device);
+/* Filling and scoring the masked entries of a weighted fit, in one fused pass (no reference .m: the definition is this comment and DESIGN 4.18).  `batch`
+ * problems travel side by side like nmfx_nmf_batch's: problem b owns the columns col_offsets[b] .. col_offsets[b + 1] - 1 (n_b >= 1) of V, M, H and Y.  V and
+ * M (>= 0 and finite) are m x N in `dtype`, column-major; W (m x K x T, or m x K x T x batch when w_per_problem != 0) and H (K x N) are laid out as
+ * nmfx_reconstruct takes them, in `dtype`, >= 0 and finite, and are rounded to fp32 images.  With
+ *   S = sum_t W(:,:,t) * rshift_t(H_b),  rshift_t(H)(:, j) = H(:, j - t), 0 before the PROBLEM's first column (ReconstructFromDecomposition.m:30-38),  on = M > 0:
+ *   Y    = on ? V : S                                                   m x N in `dtype`, or NULL
+ *   fit  = sum_{on} M .* d(V, S),   held = sum_{not on} d(V, S)         [batch] doubles each, or NULL
+ *   d:   NMFX_DIV_EUCLIDEAN 0.5*(V - S).^2;   NMFX_DIV_KL  V.*log(V./S) - V + S;   NMFX_DIV_IS  log(S./V) + V./S - 1
+ * S is fp32 arithmetic whatever dtype is (with NMFX_F64 a filled entry is the fp32 value widened); the cost terms are float64 on (double)V, (double)S.  The
+ * pass selects on M and never multiplies by it: where M > 0, Y is V's value bit for bit (NaN and Inf included); where M == 0, Y does not depend on V.  The
+ * scores read V everywhere: the caller sees to it that the hidden entries are known.  Y, fit and held may be asked for together (one pass); `divergence`
+ * is read only when fit or held is given.
+ * NMFX_ERR_INVALID: a NULL V, M, W, H or col_offsets, a size or batch <= 0, another dtype, col_offsets that do not start at 0, increase and end at N, Y, fit
+ * and held all NULL, fit or held with a divergence that is none of the three; NMFX_ERR_UNSUPPORTED: T > 64, NMFX_DIV_AB.  n_b < T - 1 is allowed.  One GPU, one
+ * kernel launch, no atomics: every 128 x 64 tile of a problem leaves one pair of float64 partials and the host adds them in tile order, so two calls return
+ * the same bits and a problem's results do not depend on its place in the batch, on the batch or on the form of W.  The call holds
+ * sizeof(dtype)*m*N*(2 + (Y != NULL)) + 4*K*(m*T*(w_per_problem ? batch : 1) + N) bytes plus 16 bytes per tile and per problem; a failed allocation is
+ * NMFX_ERR_NOMEM with the byte count.  Environment, read per call: NMFX_IMPUTE_MAX_GRID lowers the workgroup count (tests).  A new entry point; no
+ * structure grows, so NMFX_VERSION stays 600.  nmfx_last_call_timing describes the call. */
+nmfx_status nmfx_impute(int64_t m, int64_t N, int32_t K, int32_t T, int32_t dtype, const void *V, const void *M, const void *W, const void *H,
+                        int32_t batch, const int64_t *col_offsets /* batch + 1, col_offsets[0] = 0, increasing */, int32_t w_per_problem,
+                        int32_t divergence, void *Y /* or NULL */, double *fit /* [batch] or NULL */, double *held /* [batch] or NULL */, int32_t device);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,

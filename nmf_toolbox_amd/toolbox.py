@@ -17,6 +17,8 @@
     W, H, cost = wcnmf(V, M, num_basis_elems, context_len, config)   cnmf.m:1 with per-entry weights M >= 0
     W, H, cost = wnmf_batch(Vs, Ms, num_basis_elems, config)      wnmf per problem (lists: B independent weighted problems in one call)
     W, H, cost = wcnmf_batch(Vs, Ms, num_basis_elems, context_len, config)   wcnmf per problem (lists: B independent weighted problems in one call)
+    Y          = impute(V, M, W, H, config)                       V where M > 0, sum_t W_t*rshift_t(H) in the holes (impute_batch: lists of B problems)
+    fit, held  = holdout(V, M, W, H, config)                      the divergence over the observed and over the hidden entries (holdout_batch: arrays of B)
 
 Same argument meaning, defaults and error behaviour as the MATLAB functions (a MATLAB cell array is
 a Python list, a struct a dict; errors are ValueError carrying the reference's message).  This file
@@ -1275,6 +1277,210 @@ def softmask_batch(Xs, W, Hs, config=None, device=0):
         Hcat[:, s0:s0 + nb] = pr[2]
     outs = _softmask_c(Xcat, Wc, Hcat, Ks, T, power, masks, device)
     return [[np.asfortranarray(o[:, s0:s0 + nb]) for o in outs] for s0, nb in zip(starts, ns)]
+
+
+IMPUTE_MAX_CONTEXT = 64
+
+
+def _impute_config(fn, cfg, scores):
+    """the config checks of impute / holdout and their batch forms -> the divergence's code (None for the filling calls, which have no divergence)"""
+    try:
+        _precision(cfg, fn)      # (raises for 'float64' / 'double': S is fp32 arithmetic, nothing runs silently in another precision)
+    except ValueError as e:
+        raise ValueError(str(e) if fn in str(e) else fn + ": " + str(e)) from None
+    if cfg.get("nmfx_gpus", None) is not None or cfg.get("nmfx_multi_backend", None) is not None:
+        raise ValueError("%s runs on one GPU: nmfx_gpus and nmfx_multi_backend are not supported" % fn)
+    div = cfg.get("divergence", "euclidean")
+    if div in ("ab_divergence", "ab"):
+        raise ValueError("%s has no alpha-beta divergence: its divergences are 'euclidean', 'kl' ('kl_divergence') and 'is' ('is_divergence')" % fn)
+    if not isinstance(div, str) or div not in _DIV_WNMF:
+        raise ValueError("%s: no cost function defined for divergence type %s ('euclidean', 'kl' / 'kl_divergence', 'is' / 'is_divergence')" % (fn, div))
+    return _DIV_WNMF[div] if scores else None
+
+
+def _impute_factors(fn, W, H, m, n, dtype, shared=None):
+    """W and H of one problem, as arrays or as lists per source (summed), against an m x n V -> W (m x K x T) and H (K x n) in `dtype`, column-major, the
+    sources side by side along K, every entry >= 0 and finite also once rounded to float32.  `shared`, a dict, keeps the travelling form of a W that
+    comes again (the batch calls' ONE W: converted and checked once, not once per problem)."""
+    if _is_cell(W) != _is_cell(H):
+        raise ValueError("%s: W and H must both be lists (one entry per source) or both be arrays" % fn)
+    Wl, Hl = (list(W), list(H)) if _is_cell(W) else ([W], [H])
+    if len(Wl) != len(Hl):
+        raise ValueError("%s: W lists %d sources, H lists %d" % (fn, len(Wl), len(Hl)))
+    if len(Wl) == 0:
+        raise ValueError("%s: W and H list no source" % fn)
+    Wr, Hr, T = [], [], None
+    for i, (w, h) in enumerate(zip(Wl, Hl)):
+        w, h = np.asarray(w), np.asarray(h)
+        for name, a in (("W", w), ("H", h)):
+            if a.dtype.kind not in "buif":
+                raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
+        if w.ndim == 2:
+            w = w.reshape(w.shape[0], w.shape[1], 1)
+        if w.ndim != 3 or h.ndim != 2:
+            raise ValueError("%s: W of source %d must be m x K_i or m x K_i x T and H must be K_i x n; got shapes %r and %r" % (fn, i, np.shape(Wl[i]), h.shape))
+        if w.shape[0] != m or h.shape[1] != n:
+            raise ValueError("%s: V is %d x %d, source %d has W with %d rows and H with %d columns" % (fn, m, n, i, w.shape[0], h.shape[1]))
+        if w.shape[1] != h.shape[0] or w.shape[1] < 1:
+            raise ValueError("%s: source %d has %d components in W and %d rows in H (K_i must agree and be >= 1)" % (fn, i, w.shape[1], h.shape[0]))
+        T = w.shape[2] if T is None else T
+        if w.shape[2] != T:
+            raise ValueError("%s: every source must have one context length T; source 0 has %d, source %d has %d" % (fn, T, i, w.shape[2]))
+        Wr.append(w)
+        Hr.append(h)
+    if T < 1 or T > IMPUTE_MAX_CONTEXT:
+        raise ValueError("%s: the context length T = %d is not supported (1 to %d)" % (fn, T, IMPUTE_MAX_CONTEXT))
+    key = (id(W), np.dtype(dtype).str)
+    Wc = shared.get(key) if shared is not None else None
+    with np.errstate(over="ignore"):     # (a float64 entry beyond float32's range is Inf in the fp32 image the device contracts, and refused)
+        Hc = _f_order(Hr[0] if len(Hr) == 1 else np.concatenate(Hr, axis=0), dtype)      # (one source in the right form is passed as it is)
+        todo = [("H", Hc)]
+        if Wc is None:
+            Wc = _f_order(Wr[0] if len(Wr) == 1 else np.concatenate(Wr, axis=1), dtype)
+            todo.insert(0, ("W", Wc))
+        for name, a in todo:
+            a32 = a if a.dtype == np.float32 else a.astype(np.float32)
+            if not np.all(np.isfinite(a32)):
+                raise ValueError("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name))
+            if a.size and a.min() < 0:
+                raise ValueError("%s: every entry of %s must be >= 0" % (fn, name))
+    if shared is not None:
+        shared[key] = Wc
+    return Wc, Hc
+
+
+def _impute_data(fn, V, M, scores, name="V", mname="M"):
+    """V as it travels (float32 stays, every other real dtype is float64; column-major) and M by wnmf's rules in V's dtype"""
+    V = np.asarray(V)
+    if V.ndim != 2:
+        raise ValueError("%s: %s must be a matrix" % (fn, name))
+    if V.dtype.kind not in "buif":
+        raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, V.dtype))
+    if V.shape[0] < 1 or V.shape[1] < 1:
+        raise ValueError("%s: %s must not be empty; got %d x %d" % (fn, name, V.shape[0], V.shape[1]))
+    V = _f_order(V, np.float32 if V.dtype == np.float32 else np.float64)
+    Mf = _weights(fn, M, V.shape, V.dtype, mname, name)
+    if scores and not np.all(np.isfinite(V)):
+        raise ValueError("%s: every entry of %s must be finite: the hidden entries must be known to be scored (%s is read where %s == 0 too)" % (fn, name, name, mname))
+    return V, Mf
+
+
+def _impute_inputs(fn, V, M, W, H, config, scores, shared=None):
+    """Everything the four calls check on one problem before the library is touched, with `fn` in every message -> V, M (travelling dtype), W (m x K x T),
+    H (K x n) and the divergence's code (None for the filling calls)"""
+    div = _impute_config(fn, config if config else {}, scores)
+    Vf, Mf = _impute_data(fn, V, M, scores)
+    Wc, Hc = _impute_factors(fn, W, H, Vf.shape[0], Vf.shape[1], Vf.dtype, shared)
+    return Vf, Mf, Wc, Hc, div
+
+
+def _impute_c(V, M, Wc, Hc, offsets, w_per_problem, div, device):
+    """the one call into nmfx_impute: V, M (m x N, the travelling dtype), Wc (m x K x T, or m x K x T x B) and Hc (K x N) in that dtype, column-major; div None
+    fills (-> Y, m x N), a divergence's code scores (-> fit, held: float64 [B])"""
+    m, N = V.shape
+    K, T = Wc.shape[1], Wc.shape[2]
+    B = len(offsets) - 1
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    lib = _lib.load()
+    dt = _lib.F32 if V.dtype == np.float32 else _lib.F64
+    if div is None:
+        Y = np.empty((m, N), dtype=V.dtype, order="F")
+        _lib.check(lib.nmfx_impute(m, N, K, T, dt, _fptr(V), _fptr(M), _fptr(Wc), _fptr(Hc), B, _fptr(off), int(bool(w_per_problem)), -1, _fptr(Y), None, None,
+                                   int(device)))
+        return Y
+    fit, held = np.zeros(B), np.zeros(B)
+    _lib.check(lib.nmfx_impute(m, N, K, T, dt, _fptr(V), _fptr(M), _fptr(Wc), _fptr(Hc), B, _fptr(off), int(bool(w_per_problem)), int(div), None, _fptr(fit),
+                               _fptr(held), int(device)))
+    return fit, held
+
+
+def impute(V, M, W, H, config=None, device=0):
+    """Y = impute(V, M, W, H, config): V where it was observed and the model in the holes -- how an inpainting with wnmf / wcnmf ends.  An extension (no
+    reference .m).  With the sources i (W_i m x K_i x T, or m x K_i when T == 1; H_i K_i x n; all >= 0 and finite):
+
+        S  = sum_i sum_t W_i(:,:,t) * rshift_t(H_i)      (ReconstructFromDecomposition.m:30-38, all sources summed)
+        Y  = M > 0 ? V : S
+
+    W and H are what nmf / cnmf / wnmf / wcnmf return: single arrays, or lists per source (summed; no 'sources' key is needed).  M follows wnmf's rules:
+    the shape of V; bool, integer or float; >= 0 and finite; it travels in V's dtype.  float32 V gives float32 Y, every other real dtype travels as
+    float64.  Where M > 0, Y is V's value bit for bit, NaN and Inf included; where M == 0, V is never looked at: it may be NaN, Inf or negative, and Y is
+    the same whatever it holds there.  S is fp32 device arithmetic on the fp32 images of W and H whatever V's dtype (the float64 call's filled entries
+    are the float32 call's, widened).  T <= 64; n < T - 1 is allowed.  One GPU: nmfx_gpus, nmfx_multi_backend and nmfx_precision='float64' are refused.
+    config['divergence'] is holdout's key and changes nothing here, but one config serves both calls: 'ab' and unknown names are refused here too."""
+    Vf, Mf, Wc, Hc, _ = _impute_inputs("impute", V, M, W, H, config, False)
+    return _impute_c(Vf, Mf, Wc, Hc, [0, Vf.shape[1]], False, None, device)
+
+
+def holdout(V, M, W, H, config=None, device=0):
+    """fit, held = holdout(V, M, W, H, config): the cost of a decomposition on the entries the fit saw and on the ones hidden from it -- how choosing K
+    by imputation error ends.  With S as in impute and d the divergence config['divergence'] names ('euclidean', the default: 0.5*(V - S).^2;
+    'kl' / 'kl_divergence': V.*log(V./S) - V + S;  'is' / 'is_divergence': log(S./V) + V./S - 1):
+
+        fit  = sum over M > 0 of M .* d(V, S)       (wnmf's data fit)
+        held = sum over M == 0 of d(V, S)           (unweighted: a hidden entry has no weight)
+
+    Two Python floats.  V is needed everywhere: a NaN or Inf anywhere in V is a ValueError (the hidden entries must be known).  The cost terms are
+    float64 on (double)V and (double)S, S in fp32 as for impute; exact zeros of V under kl / is give what the expressions give (NaN / Inf).  An empty
+    hole set gives held == 0.0, an empty observed set fit == 0.0.  No atomics: two calls return the same bits.  Inputs and refusals are impute's, plus
+    'ab' and unknown divergences."""
+    Vf, Mf, Wc, Hc, div = _impute_inputs("holdout", V, M, W, H, config, True)
+    fit, held = _impute_c(Vf, Mf, Wc, Hc, [0, Vf.shape[1]], False, div, device)
+    return float(fit[0]), float(held[0])
+
+
+def _impute_batch(fn, Vs, Ms, Ws, Hs, config, scores, device):
+    """The batch forms: the problems side by side, their column offsets, one W or one per problem.  Ws is per problem when it is nested as deep as Hs: a
+    list of B arrays beside single-source Hs[b] (arrays), a list of B lists beside Hs[b] that are lists per source; otherwise it is ONE W (an array, or
+    a list per source beside Hs[b] that are lists per source), shared."""
+    if not _is_cell(Vs) or not _is_cell(Ms) or not _is_cell(Hs) or len(Vs) == 0:
+        raise ValueError("%s: Vs, Ms and Hs must be lists of the same length >= 1 (one entry per problem)" % fn)
+    B = len(Vs)
+    if len(Ms) != B or len(Hs) != B:
+        raise ValueError("%s: Vs lists %d problems, Ms %d and Hs %d: the lists must have the same length" % (fn, B, len(Ms), len(Hs)))
+    per_problem = _is_cell(Ws) and (not _is_cell(Hs[0]) or (len(Ws) > 0 and _is_cell(Ws[0])))
+    if per_problem and len(Ws) != B:
+        raise ValueError("%s: Ws lists %d dictionaries for %d problems (ONE W for every problem, or a list of one per problem)" % (fn, len(Ws), B))
+    shared = None if per_problem else {}
+    probs = [_impute_inputs(fn, Vs[b], Ms[b], Ws[b] if per_problem else Ws, Hs[b], config, scores, shared) for b in range(B)]
+    V0, _, W0, _, div = probs[0]
+    for b, pr in enumerate(probs):
+        if pr[0].shape[0] != V0.shape[0]:
+            raise ValueError("%s: every problem must have the same number of rows; Vs[0] has %d, Vs[%d] has %d" % (fn, V0.shape[0], b, pr[0].shape[0]))
+        if pr[0].dtype != V0.dtype:
+            raise ValueError("%s: every Vs[b] must travel in one dtype; Vs[0] is %s, Vs[%d] is %s" % (fn, V0.dtype, b, pr[0].dtype))
+        if pr[2].shape != W0.shape:
+            raise ValueError("%s: the problems must share K and T; Ws[0] is m x %d x %d, Ws[%d] is m x %d x %d" % ((fn,) + W0.shape[1:] + (b,) + pr[2].shape[1:]))
+    off = np.concatenate([[0], np.cumsum([pr[0].shape[1] for pr in probs])]).astype(np.int64)
+    Vcat = np.asfortranarray(np.concatenate([pr[0] for pr in probs], axis=1))
+    Mcat = np.asfortranarray(np.concatenate([pr[1] for pr in probs], axis=1))
+    Hcat = np.asfortranarray(np.concatenate([pr[3] for pr in probs], axis=1))
+    Wc = W0
+    if per_problem:      # m x K x T x B, column-major: problem b's image is one contiguous block
+        Wc = np.empty(W0.shape + (B,), dtype=W0.dtype, order="F")
+        for b, pr in enumerate(probs):
+            Wc[:, :, :, b] = pr[2]
+    out = _impute_c(Vcat, Mcat, Wc, Hcat, off, per_problem, div, device)
+    if scores:
+        return out
+    return [np.asfortranarray(out[:, off[b]:off[b + 1]]) for b in range(B)]
+
+
+def impute_batch(Vs, Ms, Ws, Hs, config=None, device=0):
+    """Ys = impute_batch(Vs, Ms, Ws, Hs, config): impute for B problems Vs[b] (m x n_b, n_b >= 1) with their weights Ms[b] and activations Hs[b], in one
+    call.  The problems share m, K and T.  Ws is ONE W shared by every problem (the trained dictionary: an array, or a list per source as for impute), or
+    a list of B of them (the per-fold, per-restart dictionaries wnmf_batch / wcnmf_batch return); a list beside single-source Hs[b] is taken as one W per
+    problem.  Ys[b] is impute(Vs[b], Ms[b], W_b, Hs[b], config) bit for bit, wherever b stands in the batch and whichever form Ws has: a problem's tiles
+    are laid from its own first column and its shifts read 0 before it, never a neighbour's H.  Every Vs[b] must travel in the same dtype.  config and the
+    refusals are impute's."""
+    return _impute_batch("impute_batch", Vs, Ms, Ws, Hs, config, False, device)
+
+
+def holdout_batch(Vs, Ms, Ws, Hs, config=None, device=0):
+    """fits, helds = holdout_batch(Vs, Ms, Ws, Hs, config): holdout for B problems in one call -- the same V under folds x restarts hold-out masks with
+    the dictionaries wnmf_batch returned, or a test set against one trained W.  Two float64 arrays of length B; entry b is holdout(Vs[b], Ms[b], W_b,
+    Hs[b], config) bit for bit (every 128 x 64 tile of a problem leaves one pair of float64 partials, added per problem in tile order: no atomics, nothing
+    depends on the batch).  Lists, Ws forms and refusals as for impute_batch; config['divergence'] as for holdout."""
+    return _impute_batch("holdout_batch", Vs, Ms, Ws, Hs, config, True, device)
 
 
 def projfunc(s, k1, k2, nn=True, device=0):
