@@ -314,6 +314,20 @@ __global__ __launch_bounds__(256, ((K <= 128 && FUNC != 4 && FUNC != 5) ? 2 : 1)
         f32x2 es2[2], er2[2], eq2[2];                         // ... and the map's state for the two pairs of the double pair in flight
         const int cvh = RAG ? tile_rows(t) - 4 * h : 0;       // streamed index 32*jb + (reg&3) + 8*(reg>>2) + 4*h of this tile is real iff its h-free part < cvh
         float es[2], er[2], eq[2];                            // element-map pipeline state: S value, reciprocal / quotient, third temporary
+        float ek[2];                                          // alpha-beta: the binary exponent of S (ab_log)
+        // alpha-beta: x.^e = 2^(e * log2 x) with an error that does not grow with |log2 x|.  x = f * 2^k with f in [0.5, 1) (v_frexp), so log2 f lies in [-1, 0] and is
+        // off by 2^-24 absolutely, where log2 x as one number is off by 2^-24 * |log2 x|; e * k = hi + lo exactly (one fma), hi = n + r with n an integer, and
+        // x.^e = ldexp(2^(r + lo + e * log2 f), n): the argument of v_exp stays below |e| + 1.  Formed as exp2(e * log2 x) the power carried a relative error of
+        // ln2 * |e| * |log2 x| * 2^-24 with a common sign: on V * 2^40 the fused cost was off by 1.5e-5 and H by a common factor (the alpha-beta
+        // cases).  x = 0 / Inf: f = 0 / Inf and k = 0, so log2 f is clamped as before and an exponent of exactly 0 still gives 2^(+-0) = 1
+        auto ab_log = [&](float x, float &k) {
+            k = (float)__builtin_amdgcn_frexp_expf(x);
+            return __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(__builtin_amdgcn_frexp_mantf(x)), -3.0e38f, 3.0e38f);
+        };
+        auto ab_pow = [&](float e, float l, float k) {
+            const float hi = e * k, lo = fmaf(e, k, -hi), n = __builtin_rintf(hi);
+            return __builtin_amdgcn_ldexpf(__builtin_amdgcn_exp2f(fmaf(e, l, (hi - n) + lo)), (int)n);
+        };
         auto emap_u = [&](int jb, int reg, int u) {           // micro-op u of element (jb, reg); R + divergence terms, nmf.m:152,206-215
             const int sl = reg & 1;
             if (FUNC == 7) return;                            // the raw partial S is what gets stored
@@ -331,10 +345,9 @@ __global__ __launch_bounds__(256, ((K <= 128 && FUNC != 4 && FUNC != 5) ? 2 : 1)
             } else if (FUNC == 5) {                           // alpha-beta: B = S.^(a+b-1), A = V.^a .* S.^(b-1); cost terms S.*(A - b/(a+b)*B)
                 // x.^0 == 1 also for x == 0 and x == Inf (MATLAB): log2(S) is clamped to +-3e38 (one v_med3_f32), so an exponent of exactly 0
                 // (beta == 1, or alpha + beta == 1) gives 2^(+-0) = 1 where 0 * (-Inf) would be NaN; any other exponent still overflows to the same 0 / Inf
-                if (u == 0) { es[sl] = sacc[jb][reg]; er[sl] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(es[sl]), -3.0e38f, 3.0e38f); }   // log2(S)
-                if (u == 1) eq[sl] = ab_e1 * er[sl];
-                if (u == 2) eq[sl] = __builtin_amdgcn_exp2f(eq[sl]);                 // S.^(b-1)
-                if (u == 3) er[sl] = __builtin_amdgcn_exp2f(ab_e2 * er[sl]);         // S.^(a+b-1)
+                if (u == 0) { es[sl] = sacc[jb][reg]; er[sl] = ab_log(es[sl], ek[sl]); }   // log2 of the mantissa of S (clamped) and its exponent
+                if (u == 2) eq[sl] = ab_pow(ab_e1, er[sl], ek[sl]);                  // S.^(b-1)
+                if (u == 3) er[sl] = ab_pow(ab_e2, er[sl], ek[sl]);                  // S.^(a+b-1)
                 if (u == 4) { eq[sl] = v * eq[sl]; sacc[jb][reg] = live ? eq[sl] : 0.0f; }
                 if (u == 5) sacc2[jb][reg] = live ? er[sl] : 0.0f;
                 if (u == 6) eq[sl] = fmaf(-ab_kappa, er[sl], eq[sl]);
@@ -351,22 +364,21 @@ __global__ __launch_bounds__(256, ((K <= 128 && FUNC != 4 && FUNC != 5) ? 2 : 1)
             } else if (FUNC == 12) {                          // IS, denominators only: B = 1./S
                 if (u == 0) sacc[jb][reg] = live ? __builtin_amdgcn_rcpf(sacc[jb][reg]) : 0.0f;
             } else if (EF == 13) {                            // alpha-beta, numerators only: A = V.^a .* S.^(b-1), cost terms S.*(A - b/(a+b)*B) (functor 5 without its B tile)
-                if (u == 0) { es[sl] = sacc[jb][reg]; er[sl] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(es[sl]), -3.0e38f, 3.0e38f); }   // log2(S), see functor 5
-                if (u == 1) eq[sl] = ab_e1 * er[sl];
-                if (u == 2) eq[sl] = __builtin_amdgcn_exp2f(eq[sl]);                 // S.^(b-1)
-                if (u == 3) er[sl] = __builtin_amdgcn_exp2f(ab_e2 * er[sl]);         // S.^(a+b-1)
+                if (u == 0) { es[sl] = sacc[jb][reg]; er[sl] = ab_log(es[sl], ek[sl]); }   // log2 of the mantissa of S (clamped) and its exponent
+                if (u == 2) eq[sl] = ab_pow(ab_e1, er[sl], ek[sl]);                  // S.^(b-1)
+                if (u == 3) er[sl] = ab_pow(ab_e2, er[sl], ek[sl]);                  // S.^(a+b-1)
                 if (u == 4) { eq[sl] = v * eq[sl]; sacc[jb][reg] = live ? eq[sl] : 0.0f; }
                 if (BQ && u == 5) bq[BQ ? jb : 0][BQ ? reg : 0] = er[sl];           // B = S.^(a+b-1)
                 if (u == 6) eq[sl] = fmaf(-ab_kappa, er[sl], eq[sl]);
                 if (u == 7) { tc = live ? fmaf(es[sl], eq[sl], tc) : tc; asm volatile("" : "+v"(tc)); }
             } else if (FUNC == 17) {                          // alpha-beta, dual form (alpha == 0): A = S.^beta ./ V
-                if (u == 0) er[sl] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(sacc[jb][reg]), -3.0e38f, 3.0e38f);   // log2(S), clamped as in functor 5
-                if (u == 1) eq[sl] = __builtin_amdgcn_exp2f(p.ab_beta * er[sl]);                                         // S.^beta
+                if (u == 0) er[sl] = ab_log(sacc[jb][reg], ek[sl]);                  // as in functor 5
+                if (u == 1) eq[sl] = ab_pow(p.ab_beta, er[sl], ek[sl]);              // S.^beta
                 if (u == 2) er[sl] = __builtin_amdgcn_rcpf(v);
                 if (u == 3) sacc[jb][reg] = live ? eq[sl] * er[sl] : 0.0f;
             } else if (FUNC == 14) {                          // alpha-beta, denominators only: B = S.^(a+b-1)
-                if (u == 0) er[sl] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(sacc[jb][reg]), -3.0e38f, 3.0e38f);
-                if (u == 1) sacc[jb][reg] = live ? __builtin_amdgcn_exp2f(ab_e2 * er[sl]) : 0.0f;
+                if (u == 0) er[sl] = ab_log(sacc[jb][reg], ek[sl]);
+                if (u == 1) sacc[jb][reg] = live ? ab_pow(ab_e2, er[sl], ek[sl]) : 0.0f;
             } else if (FUNC == 6) {                           // residual: R = S - V, cost terms (S - V).^2   (nmfsc.m:139,148)
                 if (u == 0) { const float e = sacc[jb][reg] - v; tc = live ? fmaf(e, e, tc) : tc; sacc[jb][reg] = live ? e : 0.0f; }
             } else if (MF >= 2) {

@@ -11,6 +11,7 @@ import numpy as np
 from conftest import EPS, synth
 
 ITERS = 6
+DUAL_ITERS = 2       # alpha = 0: the reference's dual equations diverge double-exponentially in float64 too (tests/test_gpu_parity.py::test_nmf_ab_divergence)
 NO_STOP = 1e-300     # the oracle has no switch for its stop rule: a tolerance no decrease can be below
 LAMBDA = 2.0 ** -54  # the sparsity of the `sparse` cases: pos + lambda against eps = 2^-52 at the mixed p
 
@@ -237,6 +238,37 @@ ADDON_ROWCOL_ROWS = tuple(r for r in ADDON_ROWS if ROWS[r]["call"] != "lnmf")
 EXTRAS = {"constrainednmf": ("Z",), "cmfwisa": ("P", "V_hat")}      # what an add-on call returns besides W, H and the cost
 
 
+# ---- the alpha-beta divergence: further values of the `div` element of a case, on the nmf and cnmf rows (the batch and weighted calls have none) ---------------
+# pair -> (alpha, beta), why it is here, and the families it runs besides `scaled`:
+#   (0.5, 1.5)   alpha + beta = 2, outer exponent 1 / alpha = 2: the W-step denominator scales as 2^(4p), the H-step one as 2^(2p) -- both guards inside fp32
+#   (2, -0.5)    outer exponent 0.5, negative beta: the W step scales as 2^(0.75p), the H step as 2^(0.25p) -- no guard inside fp32
+#   (0.5, 0.5)   alpha + beta = 1: S.^(a+b-1) is the zero-exponent path, the W-step denominator is (ones * H').^2; the H-step one does not scale
+#   (1.5, -1.5)  alpha + beta = 0: the cost divides by zero in every entry (the same-pattern rule); W and H finite
+#   (0, 1)       the dual form, DUAL_ITERS iterations, |p| <= 20
+AB = {"ab_a0.5_b1.5": (0.5, 1.5), "ab_a2_b-0.5": (2.0, -0.5), "ab_a0.5_b0.5": (0.5, 0.5), "ab_a1.5_b-1.5": (1.5, -1.5), "ab_a0_b1": (0.0, 1.0)}
+AB_FAMILIES = {"ab_a0.5_b1.5": ("tilted", "zeros_v", "zeros_wh"), "ab_a2_b-0.5": ("tilted",), "ab_a0.5_b0.5": ("zeros_wh",), "ab_a1.5_b-1.5": (), "ab_a0_b1": ()}
+# (which map a row runs under alpha-beta and is: the exp2 / log2 maps of fused_kernel.h on nmf_padded_k7, nmf_fused_*, cnmf_padded_k5; nmf_k257 -- the column-block
+# chain takes K % 32 == 0 -- and cnmf_fused_k32 / k64 -- the stored-maps S pass takes m % 4 == 0 -- fall to the powf maps of the generic kernels)
+AB_ROWS = tuple(r for r in ROWS if ROWS[r]["call"] in ("nmf", "cnmf"))
+AB_FEW_ROWS = ("nmf_generic", "nmf_fused_k32", "nmf_fused_k256", "nmf_k257", "cnmf_fused_k32", "nmf_f64")      # the rows of (1.5, -1.5) and of the dual form: one per path class
+AB_DUAL_MAX_P = 20
+
+
+def ab_pair(div):
+    """(alpha, beta) of an alpha-beta case, None for euclidean / kl / is"""
+    return AB.get(div)
+
+
+def ab_divs(row):
+    if row not in AB_ROWS:
+        return ()
+    return tuple(d for d in AB if row in AB_FEW_ROWS or d not in ("ab_a1.5_b-1.5", "ab_a0_b1"))
+
+
+def iters(div):
+    return DUAL_ITERS if AB.get(div, (1.0, 1.0))[0] == 0 else ITERS
+
+
 def shapes(row, family="scaled"):
     """the (m, n, K, T) of every problem of a row (T = None: no context); one problem unless the call is a batch"""
     r = ROWS[row]
@@ -361,6 +393,62 @@ IS_HGUARD_P = 57
 BATCH_HGUARD_P = {("wnmfbatch_70x5_mask", "euclidean"): -52, ("wnmfbatch_70x5_weights", "euclidean"): -52}
 
 
+# The scaled exponents of the alpha-beta cases per (key(row), pair), from regime_oracle._ab_iterations (the float64 restatement with `pos` taken after the outer
+# exponent) and pinned by tests/test_regime_inputs_host.py.  mixed / clamped: the W-step guard, as in SCALED_P (a half-integer where no integer has 10-90 %);
+# `sparse` runs the mixed p with lambda = 2^-54.  m / p: the largest |p| <= 40 of either sign (20 for the dual form) at which everything stays a normal fp32 number
+# with the factor 2^20 to spare (test_ab_range_tags_are_the_largest_inside_fp32); m only where no p inside fp32 reaches a guard.  What is left out, and why:
+#   (0.5, 1.5)   clamped at K <= 64 and on the cnmf keys: the guarded quantity is pos.^2, which is below 2^-106 as soon as every entry is below eps = 2^-52
+#                (p = -17) unless the sums are long -- K >= 96 keeps a binade.  hguard / hsparse on every key: the H-step guard replaces 10 % of its
+#                denominators from p = -24 ... -26 on, where the W step has been clamped for eight binades: its denominator after the outer power is at
+#                2^-115 and below, at K <= 64 and under cnmf the cost terms V.^a .* S.^b are below 2^-147 (test_ab_hguard_is_outside_fp32).
+#                The upper end is p = 18 ... 23, not 40: the W-step pair scales as 2^(4p)
+#   (0.5, 0.5)   no hguard: the H-step denominator (W' * ones).^2 does not scale
+#   (2, -0.5), (1.5, -1.5), (0, 1)   no guard is reached inside fp32 (the W step scales as 2^(0.75p), 2^0 and 2^p with |p| <= 20): m and p alone
+AB_P = {
+    ("nmf_96x130x7", "ab_a0.5_b1.5"): dict(mixed=-15.5, p=23),
+    ("nmf_129x131x32", "ab_a0.5_b1.5"): dict(mixed=-15, p=22),
+    ("nmf_64x131x32", "ab_a0.5_b1.5"): dict(mixed=-15, p=22),
+    ("nmf_200x70x64", "ab_a0.5_b1.5"): dict(mixed=-14.5, p=23),
+    ("nmf_129x200x96", "ab_a0.5_b1.5"): dict(mixed=-15, clamped=-18, p=21),
+    ("nmf_130x257x160", "ab_a0.5_b1.5"): dict(mixed=-15, clamped=-19, p=21),
+    ("nmf_257x129x256", "ab_a0.5_b1.5"): dict(mixed=-14, clamped=-18, p=21),
+    ("nmf_150x260x257", "ab_a0.5_b1.5"): dict(mixed=-14, clamped=-19, p=21),
+    ("cnmf_96x130x5x3", "ab_a0.5_b1.5"): dict(mixed=-15, p=20),
+    ("cnmf_129x333x32x4", "ab_a0.5_b1.5"): dict(mixed=-15, p=18),
+    ("cnmf_129x333x64x2", "ab_a0.5_b1.5"): dict(mixed=-15, p=18),
+    ("nmf_96x130x7", "ab_a2_b-0.5"): dict(m=-38, p=40),
+    ("nmf_129x131x32", "ab_a2_b-0.5"): dict(m=-38, p=40),
+    ("nmf_64x131x32", "ab_a2_b-0.5"): dict(m=-39, p=40),
+    ("nmf_200x70x64", "ab_a2_b-0.5"): dict(m=-38, p=40),
+    ("nmf_129x200x96", "ab_a2_b-0.5"): dict(m=-38, p=40),
+    ("nmf_130x257x160", "ab_a2_b-0.5"): dict(m=-38, p=40),
+    ("nmf_257x129x256", "ab_a2_b-0.5"): dict(m=-38, p=40),
+    ("nmf_150x260x257", "ab_a2_b-0.5"): dict(m=-34, p=40),
+    ("cnmf_96x130x5x3", "ab_a2_b-0.5"): dict(m=-38, p=40),
+    ("cnmf_129x333x32x4", "ab_a2_b-0.5"): dict(m=-34, p=40),
+    ("cnmf_129x333x64x2", "ab_a2_b-0.5"): dict(m=-34, p=40),
+    ("nmf_96x130x7", "ab_a0.5_b0.5"): dict(mixed=-33, clamped=-36, p=40),
+    ("nmf_129x131x32", "ab_a0.5_b0.5"): dict(mixed=-31, clamped=-34, p=40),
+    ("nmf_64x131x32", "ab_a0.5_b0.5"): dict(mixed=-31, clamped=-34, p=40),
+    ("nmf_200x70x64", "ab_a0.5_b0.5"): dict(mixed=-30, clamped=-33, p=40),
+    ("nmf_129x200x96", "ab_a0.5_b0.5"): dict(mixed=-30, clamped=-34, p=40),
+    ("nmf_130x257x160", "ab_a0.5_b0.5"): dict(mixed=-30, clamped=-34, p=40),
+    ("nmf_257x129x256", "ab_a0.5_b0.5"): dict(mixed=-29, clamped=-33, p=40),
+    ("nmf_150x260x257", "ab_a0.5_b0.5"): dict(mixed=-29, clamped=-34, p=40),
+    ("cnmf_96x130x5x3", "ab_a0.5_b0.5"): dict(mixed=-31, clamped=-36, p=40),
+    ("cnmf_129x333x32x4", "ab_a0.5_b0.5"): dict(mixed=-30, clamped=-38, p=40),
+    ("cnmf_129x333x64x2", "ab_a0.5_b0.5"): dict(mixed=-30, clamped=-37, p=40),
+    ("nmf_129x131x32", "ab_a1.5_b-1.5"): dict(m=-40, p=40),
+    ("nmf_257x129x256", "ab_a1.5_b-1.5"): dict(m=-40, p=39),
+    ("nmf_150x260x257", "ab_a1.5_b-1.5"): dict(m=-40, p=38),
+    ("cnmf_129x333x32x4", "ab_a1.5_b-1.5"): dict(m=-40, p=37),
+    ("nmf_129x131x32", "ab_a0_b1"): dict(m=-20, p=20),
+    ("nmf_257x129x256", "ab_a0_b1"): dict(m=-20, p=20),
+    ("nmf_150x260x257", "ab_a0_b1"): dict(m=-20, p=20),
+    ("cnmf_129x333x32x4", "ab_a0_b1"): dict(m=-20, p=20),
+}
+
+
 # `sens` per key: the largest movement of the float64 reference, over the cases of the key, when W_init and H_init are rounded to fp32 once -- (on W, H and the further
 # outputs; on the cost).  nmfsc, cnmfsc and cmfwisa allow max(contract, 2 * sens) in their own files; every figure here is below a twentieth of the contract, so the
 # contract alone is the bar of these rows.  Computed and pinned by tests/test_regime_inputs_host.py::test_reference_sensitivity (within a factor 2)
@@ -381,6 +469,13 @@ SENS = {
 def scaled_tags(row, div):
     """the scaled cases of (row, div): tag -> (p, lambda)"""
     call = ROWS[row]["call"]
+    if div in AB:
+        ps = AB_P[(key(row), div)]
+        tags = {t: (ps[t], 0.0) for t in ("mixed", "clamped") if t in ps}
+        tags.update({"%s%g" % (t, abs(ps[t])): (ps[t], 0.0) for t in ("m", "p") if t in ps})      # m38: p = -38; p21: p = +21
+        if "mixed" in ps:
+            tags["sparse"] = (ps["mixed"], LAMBDA)
+        return tags
     if call == "cmfwisa":      # a pair of exponents per guard; lambda (H_sparsity) sits in the H-step guard, so `sparse` runs at the H-step mixed exponent
         mixed, clamped, hmixed, hclamped = SCALED_P[(key(row), div)]
         tags = {"mixed": (mixed, 0.0), "clamped": (clamped, 0.0), "hmixed": (hmixed, 0.0), "hclamped": (hclamped, 0.0), "p40": (40, 0.0), "sparse": (hmixed, LAMBDA)}
@@ -453,7 +548,36 @@ TILT_RATIO = {
     ("cmfwisa_64x96_5+8", "euclidean"): (1.14, 1.0),
     ("cmfwisa_64x96_2+3+2+4+3", "euclidean"): (1.07, 1.14),
     ("cmfwisa_65x130_5+3", "euclidean"): (1.56, 1.18),
+    ("nmf_96x130x7", "ab_a0.5_b1.5"): (46.3, 3.79),
+    ("nmf_96x130x7", "ab_a2_b-0.5"): (10.6, 1.82),
+    ("nmf_129x131x32", "ab_a0.5_b1.5"): (13.4, 2.4),
+    ("nmf_129x131x32", "ab_a2_b-0.5"): (4.46, 2.29),
+    ("nmf_64x131x32", "ab_a0.5_b1.5"): (12, 1.93),
+    ("nmf_64x131x32", "ab_a2_b-0.5"): (4.37, 2.24),
+    ("nmf_200x70x64", "ab_a0.5_b1.5"): (8.63, 2.23),
+    ("nmf_200x70x64", "ab_a2_b-0.5"): (4.03, 1.87),
+    ("nmf_129x200x96", "ab_a0.5_b1.5"): (9.17, 2.35),
+    ("nmf_129x200x96", "ab_a2_b-0.5"): (3.79, 1.88),
+    ("nmf_130x257x160", "ab_a0.5_b1.5"): (8.75, 2.59),
+    ("nmf_130x257x160", "ab_a2_b-0.5"): (3.79, 1.94),
+    ("nmf_257x129x256", "ab_a0.5_b1.5"): (7.05, 2.04),
+    ("nmf_257x129x256", "ab_a2_b-0.5"): (3.43, 1.83),
+    ("nmf_150x260x257", "ab_a0.5_b1.5"): (6.44, 2.37),
+    ("nmf_150x260x257", "ab_a2_b-0.5"): (3.43, 1.98),
+    ("cnmf_96x130x5x3", "ab_a0.5_b1.5"): (7.09, 1.9),
+    ("cnmf_96x130x5x3", "ab_a2_b-0.5"): (2.75, 1.66),
+    ("cnmf_129x333x32x4", "ab_a0.5_b1.5"): (3.65, 1.63),
+    ("cnmf_129x333x32x4", "ab_a2_b-0.5"): (2.03, 1.64),
+    ("cnmf_129x333x64x2", "ab_a0.5_b1.5"): (4.37, 2.06),
+    ("cnmf_129x333x64x2", "ab_a2_b-0.5"): (2.51, 1.64),
 }
+
+
+# The cancellation of the reference's alpha-beta cost, regime_oracle.kappa: the largest of |sum V.^a S.^b|, |a/(a+b) sum V.^(a+b)|, |b/(a+b) sum S.^(a+b)| over
+# |a b cost|, per pair the largest over its cases and iterations (every one at the upper end of the scaled range; at negative p the constant m n / (a (a+b)) is
+# the whole cost and kappa falls to 1e-12 and below).  tests/test_regime_inputs_host.py holds every case to 1e3 and pins these to 1 %; the GPU file takes
+# the cost bar of a case from its kappa.  The two pairs whose cost is not finite have none
+AB_KAPPA_MAX = {"ab_a0.5_b1.5": 7.44, "ab_a2_b-0.5": 11.4, "ab_a0.5_b0.5": 18.9}
 
 
 def problems(row, family, div, tag=""):
@@ -499,6 +623,10 @@ def cases():
                 out.append((row, "tilted", div, ""))
         if row in ADDON_ROWCOL_ROWS:
             out.append((row, "zeros_v", "euclidean", "rowcol"))
+    for row in AB_ROWS:      # the alpha-beta cases, behind the others: the ids and the order of the earlier cases stay as they were
+        for div in ab_divs(row):
+            out += [(row, "scaled", div, tag) for tag in scaled_tags(row, div)]
+            out += [(row, family, div, "") for family in AB_FAMILIES[div]]
     return out
 
 

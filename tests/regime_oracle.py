@@ -10,8 +10,14 @@ from conftest import EPS
 from wcnmf_oracle import _maps, lshift, reconstruct, rshift
 
 
+def div_config(div):
+    """the divergence keys of a case: an alpha-beta id (regime_inputs.AB) becomes divergence = "ab" with its exponents"""
+    ab = R.ab_pair(div)
+    return dict(divergence=div) if ab is None else dict(divergence="ab", alpha=ab[0], beta=ab[1])
+
+
 def _cfg(div, W0, H0, lam):
-    return dict(divergence=div, W_init=W0, H_init=H0, maxiter=R.ITERS, tolerance=R.NO_STOP, nmfx_disable_stop=True, W_sparsity=lam, H_sparsity=lam)
+    return dict(div_config(div), W_init=W0, H_init=H0, maxiter=R.iters(div), tolerance=R.NO_STOP, nmfx_disable_stop=True, W_sparsity=lam, H_sparsity=lam)
 
 
 def run_one(row, M, prob, div, lam, trace=None):
@@ -86,6 +92,9 @@ def iterations(row, M, prob, div, lam):
     if call in R.ADDON_CALLS and call != "wnmf_batch":
         with np.errstate(all="ignore"):
             return ADDON_ITERATIONS[call](row, prob, div, lam)
+    if R.ab_pair(div) is not None:
+        with np.errstate(all="ignore"):
+            return _ab_iterations(row, prob, div, lam)
     V, W0, H0 = prob
     M = np.ones_like(V) if M is None else M
     on = M > 0
@@ -147,6 +156,100 @@ def iterations(row, M, prob, div, lam):
                             lambda_decides=float(np.mean(np.concatenate([g.ravel() for g in gl]))), mags=mags))
             Wp, Hp = Wn, Hn
     return out
+
+
+def _ab_iterations(row, prob, div, lam):
+    """nmf.m:157-164,188-195,213-214 / cnmf.m:179-194,209-231 restated for the alpha-beta divergence with everything an fp32 path forms kept: the powers
+    V.^a, S.^(b-1), S.^(a+b-1) (dual form, alpha = 0: V.^(a-1), S.^b, V.^(a+b-1)), both element maps, the numerator / denominator pair of either step
+    before and after the outer exponent 1 / alpha (1 / beta) -- `pos` of the guard fractions is the one AFTER it, as in max(pos.^(1/alpha) + lambda, eps) --, V.^(a+b)
+    and the three sums of the cost with their cancellation kappa (None where the cost is not finite).  Ends where the oracle ends"""
+    from oracle.nmf_oracle import _pw
+    a, b = R.ab_pair(div)
+    call = R.ROWS[row]["call"]
+    V, W0, H0 = prob
+    W, H = _normalised_init(call, W0, H0)
+    W = W.reshape(W.shape[0], W.shape[1], -1).copy()
+    H = H.copy()
+    T = W.shape[2]
+    dual = a == 0
+    ex = 1.0 / b if dual else 1.0 / a
+
+    def maps(S, mags):
+        if dual:
+            p1, p2, B = _pw(V, a - 1), _pw(S, b), _pw(V, a + b - 1)
+        else:
+            p1, p2, B = _pw(V, a), _pw(S, b - 1), _pw(S, a + b - 1)
+        A = p1 * p2
+        for nm, x in (("V_hat", S), ("pow_V", p1), ("pow_S", p2), ("A", A), ("B", B)):
+            mags.note(nm, x)
+        return A, B
+
+    out, cost = [], []
+    for it in range(R.iters(div)):
+        mags = _Mags()
+        mags.note("V", V)
+        A, B = maps(reconstruct(W, H), mags)
+        gw, gl = [], []
+        Wn = np.empty_like(W)
+        for t in range(T):
+            Hs, Wt = rshift(H, t), W[:, :, t]
+            N, P = A @ Hs.T, B @ Hs.T
+            neg_in, pos_in = N + Wt * np.sum(Wt * P, axis=0)[None, :], P + Wt * np.sum(Wt * N, axis=0)[None, :]
+            neg, pos = _pw(neg_in, ex), _pw(pos_in, ex)
+            gw.append(pos + lam < EPS)
+            gl.append((pos < EPS) & (pos + lam >= EPS))
+            for nm, x in (("W_num", N), ("W_den", P), ("W_neg_in", neg_in), ("W_pos_in", pos_in), ("W_neg", neg), ("W_pos", pos), ("W_quot", neg / np.fmax(pos + lam, EPS))):
+                mags.note(nm, x)
+            Wn[:, :, t] = Wt * (neg / np.fmax(pos + lam, EPS))
+        mags.note("W_raw", Wn)
+        if call == "nmf":
+            W = Wn * (1.0 / np.sqrt(np.sum(Wn ** 2, axis=(0, 2))))[None, :, None]
+        else:
+            W = Wn / (np.sqrt(np.sum(Wn ** 2, axis=(0, 2))) / T)[None, :, None]
+        A, B = maps(reconstruct(W, H), mags)
+        Gn, Gp = np.zeros_like(H), np.zeros_like(H)
+        for t in range(T):
+            Wt = np.ascontiguousarray(W[:, :, t])
+            Gn += Wt.T @ lshift(A, t)
+            Gp += Wt.T @ lshift(B, t)
+        neg, pos = _pw(Gn, ex), _pw(Gp, ex)
+        for nm, x in (("H_num", Gn), ("H_den", Gp), ("H_neg", neg), ("H_pos", pos), ("H_quot", neg / np.fmax(pos + lam, EPS))):
+            mags.note(nm, x)
+        H = H * (neg / np.fmax(pos + lam, EPS))
+        S = reconstruct(W, H)
+        mags.note("H", H)
+        mags.note("V_hat", S)
+        terms = (V ** a * S ** b, V ** (a + b), S ** (a + b))
+        for x in terms:
+            mags.note("cost_terms", x)
+        ab = np.float64(a) * np.float64(b)
+        d = (np.float64(-1.0) / ab) * np.sum(terms[0] - (a * terms[1] + b * terms[2] + b) / np.float64(a + b))
+        cost.append(d + lam * (np.sum(np.abs(W)) + np.sum(np.abs(H))))
+        kappa = None
+        if np.isfinite(cost[-1]):
+            sums = (np.sum(terms[0]), a / (a + b) * np.sum(terms[1]), b / (a + b) * np.sum(terms[2]))
+            for x in sums + (cost[-1],):
+                mags.note("cost", x)
+            kappa = float(np.max(np.abs(sums)) / np.abs(ab * d))
+        out.append(dict(guard_W=float(np.mean(np.concatenate([g.ravel() for g in gw]))), guard_H=float(np.mean(pos + lam < EPS)),
+                        lambda_decides=float(np.mean(np.concatenate([g.ravel() for g in gl]))), mags=mags, kappa=kappa))
+    ref = run_one(row, None, prob, div, lam)
+    _ends_where((W.reshape(np.shape(ref[0])), H, cost), ref, "alpha-beta restated")
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _kappa(key, row, family, div, tag):
+    probs, lam = R.problems(row, family, div, tag)
+    ks = [i["kappa"] for p in probs for i in iterations(row, None, p, div, lam)]
+    return None if any(k is None for k in ks) else max(ks)
+
+
+def kappa(row, family, div, tag=""):
+    """the cancellation of the reference's alpha-beta cost on a case, the largest over its iterations: max(|sum V.^a S.^b|, |a/(a+b) sum V.^(a+b)|,
+    |b/(a+b) sum S.^(a+b)|) / |a b cost|; None where the cost is not finite.  The GPU file takes its cost bar from it"""
+    first = next(r for r in R.ROWS if R.key(r) == R.key(row))
+    return _kappa(R.key(row), first, family, div, tag)
 
 
 def row_movement(row, M, prob, div):

@@ -4,6 +4,8 @@ guard as often as their names say, and everything an fp32 path forms on them is 
 sensitivity ratios of the tilted cases are the constants stored next to the inputs.  For the add-on calls (regime_inputs.ADDON_ROWS) the steps are restated in
 tests/regime_oracle.py with their denominators kept, and every restatement must end where the oracle ends; FP32_HELD names what the device holds in fp32 where a call keeps the
 rest in float64."""
+import re
+
 import numpy as np
 import pytest
 
@@ -41,6 +43,18 @@ def test_every_row_of_the_table_is_covered():
     assert {c[0] for c in R.cases() if c[1] == "zeros_v"} == set(R.ZEROS_V_ROWS + R.ADDON_ROWS)
     assert {R.ROWS[r]["call"] for r in R.ADDON_ROWS} == set(R.ADDON_CALLS)
     assert len(R.cases()) == len(set(R.cases()))
+    # the alpha-beta cases: every nmf and cnmf row, behind the others; (0.5, 1.5) in every family, (2, -0.5) scaled and tilted, (0.5, 0.5) scaled and zeros_wh,
+    # (1.5, -1.5) and the dual form scaled on one row per path class
+    ab = [c for c in R.cases() if R.ab_pair(c[2]) is not None]
+    assert R.cases()[-len(ab):] == ab and {R.ROWS[r]["call"] for r in R.AB_ROWS} == {"nmf", "cnmf"} and len(R.AB_ROWS) == 14
+    fam = lambda div: {(c[0], c[1]) for c in ab if c[2] == div}
+    assert fam("ab_a0.5_b1.5") == {(r, f) for r in R.AB_ROWS for f in ("scaled", "tilted", "zeros_v", "zeros_wh")}
+    assert fam("ab_a2_b-0.5") == {(r, f) for r in R.AB_ROWS for f in ("scaled", "tilted")}
+    assert fam("ab_a0.5_b0.5") == {(r, f) for r in R.AB_ROWS for f in ("scaled", "zeros_wh")}
+    assert fam("ab_a1.5_b-1.5") == fam("ab_a0_b1") == {(r, "scaled") for r in R.AB_FEW_ROWS}
+    assert set(R.AB_P) == {(R.key(r), d) for r in R.AB_ROWS for d in R.ab_divs(r)}
+    for (k, d), ps in R.AB_P.items():
+        assert set(ps) <= {"mixed", "clamped", "m", "p"} and "p" in ps and ("m" in ps) != ("mixed" in ps), (k, d, ps)
 
 
 @pytest.mark.parametrize("case", CASES, ids=R.case_id)
@@ -53,7 +67,7 @@ def test_reference_is_finite_with_the_expected_cost_pattern(case):
         W, H, c = ref[:3]
         assert np.array_equal(V, V.astype(np.complex64 if np.iscomplexobj(V) else np.float32).astype(V.dtype))          # the device's fp32 copy of V is lossless
         # (nmfsc with a sparse W ends its first W line search by step-size underflow, nmfsc.m:221-225, on every input here: the H of that one step and one cost come back)
-        assert np.all(np.isfinite(W)) and np.all(np.isfinite(H)) and len(c) == (1 if R.ROWS[row].get("sc") == (0.4, 0.0) else R.ITERS + ("sc" in R.ROWS[row]))
+        assert np.all(np.isfinite(W)) and np.all(np.isfinite(H)) and len(c) == (1 if R.ROWS[row].get("sc") == (0.4, 0.0) else R.iters(div) + ("sc" in R.ROWS[row]))
         assert len(ref) == 3 + len(R.EXTRAS.get(R.ROWS[row]["call"], ())) and all(np.all(np.isfinite(x)) for x in ref[3:])      # Z; P and V_hat
         if isinstance(W0, list):                                                    # cmfwisa: the sources side by side, as the reference returns them
             W0, H0 = np.hstack(W0), np.vstack(H0)
@@ -61,7 +75,11 @@ def test_reference_is_finite_with_the_expected_cost_pattern(case):
             assert np.all(np.isnan(c))                                              # 0 * log(0)
         elif family == "zeros_v" and div == "is":
             assert np.all(np.isposinf(c))                                           # log(V_hat / 0)
-        else:
+        elif div == "ab_a1.5_b-1.5":
+            assert np.all(np.isposinf(c))                                           # alpha + beta = 0: every element divides by zero
+        elif div == "ab_a0_b1":
+            assert np.all(np.isposinf(c))                                           # alpha * beta = 0: -1 / 0 times a negative sum
+        else:                                                                       # zeros_v under alpha-beta included: V.^a = 0 and nothing divides by V
             assert np.all(np.isfinite(c)) and np.all(c > 0)
         if family == "zeros_v":
             z = V == 0
@@ -104,6 +122,8 @@ def test_scaled_guard_fractions(case):
         return
     gw = np.array([[i[which] for i in prob] for prob in its])                # problems x iterations (every problem has the same number of W entries)
     pooled = gw.mean(axis=0)
+    if R.ab_pair(case[2]) is not None:      # no alpha-beta case reaches the H-step guard (test_ab_hguard_is_outside_fp32): the copies behind the outer exponent of the H step have no case
+        assert max(i["guard_H"] for prob in its for i in prob) == 0.0
     print(case, np.round(pooled, 3))
     if case[3] == "clamped" and r.get("once"):                                   # lnmf re-balances after one step: all of the first iteration's, none later
         assert gw[:, 0].min() >= 0.99 and (gw.shape[1] == 1 or gw[:, 1:].max() == 0.0), gw      # (nmfsc / cnmfsc: the first iteration alone is restated)
@@ -124,7 +144,10 @@ def test_scaled_guard_fractions(case):
         assert lam == R.LAMBDA and np.any((pooled + ld >= 0.10) & (ld >= 0.01)), (pooled, ld)
 
 
-@pytest.mark.parametrize("case", [c for c in SCALED if c[3] in ("p40", "m40")], ids=R.case_id)
+RANGE_TAG = re.compile(r"[pm]\d+$")      # p40, m40; under alpha-beta also the largest |p| below 40 that stays inside fp32 (m38, p21)
+
+
+@pytest.mark.parametrize("case", [c for c in SCALED if RANGE_TAG.match(c[3])], ids=R.case_id)
 def test_unscaled_regime_never_reaches_the_guard(case):
     """(a problem with n < T has time slices of W that meet no column of H: their numerators and denominators are exactly 0 at every scale, and are left out)"""
     its, _ = _iterations(case)
@@ -145,6 +168,76 @@ def test_scaled_stays_inside_fp32(case):
                 if held is not None and name not in held:
                     continue
                 assert lo >= F32_MIN * SPARE and hi <= F32_MAX / SPARE, (case, name, np.log2(lo), np.log2(hi))
+
+
+AB_CASES = [c for c in CASES if R.ab_pair(c[2]) is not None]
+
+
+@pytest.mark.parametrize("case", [c for c in AB_CASES if c[1] == "scaled" and RANGE_TAG.match(c[3])], ids=R.case_id)
+def test_ab_range_tags_are_the_largest_inside_fp32(case):
+    """the m / p exponents of regime_inputs.AB_P: 40 (20 for the dual form), or one binade further leaves the 2^20 margin of test_scaled_stays_inside_fp32"""
+    row, _, div, tag = case
+    p = R.scaled_tags(row, div)[tag][0]
+    limit = R.AB_DUAL_MAX_P if R.ab_pair(div)[0] == 0 else 40
+    assert p == int(p) and 0 < abs(p) <= limit and tag == ("p%d" if p > 0 else "m%d") % abs(p)
+    if abs(p) == limit:
+        return
+    m, n, K, T = R.shapes(row)[0]
+    its = RO.iterations(row, None, R.scaled(m, n, K, T, p=p + (1 if p > 0 else -1)), div, 0.0)
+    out = [(name, np.log2(lo), np.log2(hi)) for i in its for name, (lo, hi) in i["mags"].items() if not (lo >= F32_MIN * SPARE and hi <= F32_MAX / SPARE)]
+    print(case, out[:3])
+    assert out
+
+
+@pytest.mark.parametrize("row", [next(r for r in R.AB_ROWS if R.key(r) == k) for k in dict.fromkeys(R.key(r) for r in R.AB_ROWS)])
+def test_ab_hguard_is_outside_fp32(row):
+    """why (0.5, 1.5) has no hguard / hsparse case: the float64 restatement does reach the H-step guard (>= 10 % of its denominators in some iteration) at some
+    p >= -30, but at every such p something an fp32 path forms has left the 2^20 margin -- the W step is clamped long before"""
+    m, n, K, T = R.shapes(row)[0]
+    reached = []
+    for p in range(-16, -31, -1):
+        its = RO.iterations(row, None, R.scaled(m, n, K, T, p=p), "ab_a0.5_b1.5", 0.0)
+        if max(i["guard_H"] for i in its) >= 0.10:
+            lo = min((v[0], name) for i in its for name, v in i["mags"].items())
+            reached.append((p, np.log2(lo[0]), lo[1]))
+            assert lo[0] < F32_MIN * SPARE, (row, p, lo)
+    print(row, reached[:2])
+    assert reached
+
+
+@pytest.mark.parametrize("case", AB_CASES, ids=R.case_id)
+def test_ab_cost_cancellation(case):
+    """kappa of the reference's alpha-beta cost (regime_oracle.kappa) exists exactly where the cost is finite, and no case asks fp32 for more than three digits of it"""
+    k = RO.kappa(*case)
+    print(case, k)
+    if case[2] in R.AB_KAPPA_MAX:
+        assert k is not None and k <= min(1e3, 1.01 * R.AB_KAPPA_MAX[case[2]])
+    else:
+        assert k is None and not np.any(np.isfinite(RO.reference(*case)[0][2]))
+
+
+@pytest.mark.parametrize("div", sorted(R.AB_KAPPA_MAX))
+def test_ab_kappa_table(div):
+    got = max(RO.kappa(*c) for c in AB_CASES if c[2] == div)
+    print(div, got)
+    assert np.isclose(got, R.AB_KAPPA_MAX[div], rtol=1e-2, atol=0)
+
+
+@pytest.mark.parametrize("div", sorted(R.AB))
+def test_zeros_v_cost_under_alpha_beta(div):
+    """with alpha >= 0 a zero of V makes V.^a = 0 (dual form: V.^(a-1) = Inf) and only the dual form divides by V: on V with 30 % zeros the reference's W, H and cost
+    are finite for every pair with alpha > 0 and alpha + beta != 0, negative beta included -- S.^b acts on V_hat, which stays positive.  (1.5, -1.5) keeps its +Inf
+    cost; the dual form turns to NaN throughout.  The GPU file runs the family under (0.5, 1.5)"""
+    row = "nmf_generic"
+    m, n, K, T = R.shapes(row)[0]
+    with np.errstate(all="ignore"):
+        W, H, c = RO.run_one(row, None, R.zeros_v(m, n, K, T), div, 0.0)
+    a, b = R.ab_pair(div)
+    if a == 0:
+        assert np.all(np.isnan(W)) and np.all(np.isnan(H)) and not np.any(np.isfinite(c))
+        return
+    assert np.all(np.isfinite(W)) and np.all(np.isfinite(H))
+    assert np.all(np.isposinf(c)) if a + b == 0 else (np.all(np.isfinite(c)) and np.all(c > 0))
 
 
 SENS_ROWS = [next(r for r in R.ADDON_ROWS if R.key(r) == k) for k in R.SENS]
