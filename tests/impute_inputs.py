@@ -87,3 +87,61 @@ def hole_error(Y, Yref, M):
 
 def rel(a, b):
     return abs(float(a) - float(b)) / max(abs(float(b)), 1e-300)
+
+
+# ---- value ranges: the families of tests/regime_inputs.py on the fused fill-and-score pass ----------------------------------------------------------------------
+# on two shapes, float32 and float64.  scaled: V and H times 2^p; tilted: the rows of W and of V times 10^(-12 i / (m - 1)), so that a row of S and of the
+# fill is 1e-12 of the first one's and only a PER-ROW figure sees it; zeros_v: 30 % of V exactly 0, in observed entries and in holes alike (kl then gives NaN
+# and is +Inf, exactly as the float64 statement does).  REGIME_P: the largest |p| of either sign at which S, V and the largest cost term of every divergence stay
+# normal fp32 numbers with a factor 2^20 to spare -- found from the statement and pinned by tests/test_impute_host.py
+REGIME_SHAPES = [(129, 200, 22, 3), (70, 90, 8, 1)]
+REGIME_P = {(129, 200, 22, 3): (-58, 47), (70, 90, 8, 1): (-56, 50)}
+REGIME_CASES = [(s, "scaled", p) for s in REGIME_SHAPES for p in REGIME_P[s]] + [(s, f, 0) for s in REGIME_SHAPES for f in ("tilted", "zeros_v")]
+BAR_ROW_FILL = BAR_FILL                # tilted: the contract on every row's holes (the fp32 restatement stays inside it: tests/test_impute_host.py)
+
+
+def regime_ident(c):
+    shape, family, p = c
+    return "%s-%s%s" % (ident(shape), family, ("_%s%d" % ("m" if p < 0 else "p", abs(p))) if family == "scaled" else "")
+
+
+@functools.lru_cache(maxsize=None)
+def regime_case(shape, family, p=0):
+    """V, M, W, H in float64, read-only; V is an fp32 value in every entry (a factor 2^p keeps it so), so both travelling dtypes carry the same numbers"""
+    V, M, W, H = case(shape)
+    m, n = V.shape
+    V = V.astype(np.float32).astype(np.float64)
+    W, H = W.copy(), H.copy()
+    if family == "scaled":
+        V, H = V * 2.0 ** p, H * 2.0 ** p
+    elif family == "tilted":
+        tilt = 10.0 ** (-12.0 * np.arange(m) / (m - 1.0))
+        W = W * tilt.reshape((m,) + (1,) * (W.ndim - 1))
+        V = (V * tilt[:, None]).astype(np.float32).astype(np.float64)
+    elif family == "zeros_v":
+        V[np.random.RandomState(3000).rand(m, n) < 0.3] = 0.0
+    else:
+        raise ValueError(family)
+    for a in (V, W, H):
+        a.setflags(write=False)
+    return V, M, W, H
+
+
+@functools.lru_cache(maxsize=None)
+def regime_ref(shape, family, p, dtype):
+    """dict(Y, S, euclidean=(fit, held), kl=..., is=...) of the float64 statement on the values that travel"""
+    V, M, W, H = regime_case(shape, family, p)
+    Vt, Mt, S = travelling(V, dtype), travelling(M, dtype), O.total(W, H)
+    out = dict(Y=O.impute(Vt, Mt, W, H, S=S), S=S)
+    for d in DIVS:
+        out[d] = O.holdout(Vt, Mt, W, H, d, S=S)
+    for a in (out["Y"], S):
+        a.setflags(write=False)
+    return out
+
+
+def row_hole_errors(Y, Yref, M):
+    """per row with at least one hole: the relative error of the fill over that row's holes"""
+    off = ~(np.asarray(M) > 0)
+    Y, Yref = np.asarray(Y, dtype=np.float64), np.asarray(Yref, dtype=np.float64)
+    return np.array([np.linalg.norm(Y[i, off[i]] - Yref[i, off[i]]) / np.linalg.norm(Yref[i, off[i]]) for i in range(Y.shape[0]) if off[i].any()])

@@ -1,5 +1,6 @@
 """Input families of the value-range tests (tests/test_regime_inputs_host.py conditions them on the CPU, tests/test_gpu_regimes.py runs them on the HIP
-paths): data scaled by 2^p down to where the max(pos + lambda, eps) guard of nmf.m:168 / cnmf.m:193 decides the update, a 12-decade tilt over the rows
+paths; the last section of cases() is the second extension: wcnmf_batch, seminmf, every family on cnmf_batch, wnmf, wcnmf and wnmf_batch, and the euclidean H-step
+guard of the float64 kernels): data scaled by 2^p down to where the max(pos + lambda, eps) guard of nmf.m:168 / cnmf.m:193 decides the update, a 12-decade tilt over the rows
 of V, exact zeros in V, exact zeros in W_init and H_init.
 
 numpy.random.RandomState is a frozen legacy generator, so both test files regenerate the same arrays; the oracle is not imported here.  Every V is rounded
@@ -126,6 +127,31 @@ def cmfwisa_problem(m, n, Ks, family, p=0, tag="", b=0):
     return V, W0, H0
 
 
+def seminmf_problem(row, family, p=0, tag=""):
+    """V = randn, W_init = 2 * rand - 1, H_init = rand + 0.2, all fp32 values (tests/seminmf_inputs.py::mixed).  scaled: V and W_init times 2^p; tilted: the rows of V
+    (rounded to fp32 again; tag `flat`: no tilt); zeros_v: 30 % of V exactly 0; zeros_h: 40 % of H_init exactly 0 in every row but the first -- the call rejects an
+    all-zero row of H, and a column of H with no positive entry leaves 0 / 0 under the square root"""
+    import seminmf_inputs as SI
+    m, n, K = ROWS[row]["shape"]
+    V, W0, H0 = SI.mixed(m, n, K, ROWS[row]["seed"])
+    if family == "scaled":
+        V, W0 = V * 2.0 ** p, W0 * 2.0 ** p
+    elif family == "tilted":
+        V = _f32(V * _tilt(m, 0 if tag == "flat" else 12))
+    elif family == "zeros_v":
+        V[np.random.RandomState(3000).rand(m, n) < 0.3] = 0.0
+        if tag == "rowcol":      # an all-zero row of V is an all-zero row of W, an all-zero column leaves H(:, j) .* sqrt((C- * H) ./ (C+ * H))
+            V[m // 3, :] = 0.0
+            V[:, n // 2] = 0.0
+    elif family == "zeros_h":
+        mh = np.random.RandomState(4500).rand(K, n) < 0.4
+        mh[0, :] = False
+        H0[mh] = 0.0
+    else:
+        raise ValueError(family)
+    return V, W0, H0
+
+
 def addon_problem(row, family, p, tag, m, n, K, T, b):
     """(V, W_init, H_init) of a problem of an add-on row (constrainednmf: Z_init in the place of H_init, K x (unlabelled samples + classes)).  Only `scaled`
     differs from the families above: it scales what reaches the guard of the call --
@@ -226,16 +252,36 @@ ROWS = {
     # wnmf_batch_inputs.PARITY["edges"] with the weights of tests/wnmf_batch_inputs.py; n_b = 9 for 1 and 5 under zeros_v / zeros_wh as in the nmf_batch row
     "wnmf_batch_mask": dict(call="wnmf_batch", shape=(70, 5), ns=(1, 5, 63, 64, 65, 130, 257), ns_zeros=(9, 63, 64, 65, 130, 257), cfg={}, divs=_ALL[:2], weights="mask"),
     "wnmf_batch_weights": dict(call="wnmf_batch", shape=(70, 5), ns=(1, 5, 63, 64, 65, 130, 257), ns_zeros=(9, 63, 64, 65, 130, 257), cfg={}, divs=_ALL[:2], weights="weights"),
+    # cnmf_batch_inputs.PARITY["edges"] with the weights of tests/wcnmf_batch_inputs.py; V is NaN wherever the weight is 0, as in that call's own inputs (problems() below)
+    "wcnmf_batch_mask": dict(call="wcnmf_batch", shape=(70, 5, 3), ns=(2, 3, 5, 63, 64, 65, 130, 257), cfg={}, divs=_ALL[:2], weights="mask"),
+    "wcnmf_batch_weights": dict(call="wcnmf_batch", shape=(70, 5, 3), ns=(2, 3, 5, 63, 64, 65, 130, 257), cfg={}, divs=_ALL[:2], weights="weights"),
+    # seminmf.m (mixed-sign V, no guard; B = W' * V on fp32 MFMA, a float64 Cholesky of H * H', H .* sqrt((B+ + C- * H) ./ (B- + C+ * H))) on the shapes of its golden cases
+    # `zero` and `k20`, inputs of tests/seminmf_inputs.py::mixed with their seeds.  The first thing an iteration does is W = V * H' / (H * H'): W_init never enters, and
+    # `scaled` (V and W_init times 2^p; H does not scale) moves W by 2^p and B, C by 2^(2p).  Families: scaled, tilted, zeros_v, zeros_h (seminmf_problem below)
+    "seminmf_k8": dict(call="seminmf", shape=(96, 300, 8), seed=1, cfg={}, divs=_ALL[:1]),
+    "seminmf_k20": dict(call="seminmf", shape=(128, 400, 20), seed=4, cfg={}, divs=_ALL[:1]),
 }
+NEW_ROWS = ("wcnmf_batch_mask", "wcnmf_batch_weights", "seminmf_k8", "seminmf_k20")      # the rows of the second extension: their cases stand behind every earlier one (cases() below)
 ADDON_CALLS = ("lnmf", "constrainednmf", "nmfsc", "cnmfsc", "cmfwisa", "wnmf_batch")
 ADDON_ROWS = tuple(r for r in ROWS if ROWS[r]["call"] in ADDON_CALLS)
-SCALED_ROWS = tuple(ROWS)
+SCALED_ROWS = tuple(r for r in ROWS if r not in NEW_ROWS)
 OTHER_ROWS = tuple(r for r in ROWS if ROWS[r]["call"] in ("nmf", "cnmf", "nmf_batch"))      # tilted, zeros_v, zeros_wh
 ZEROS_V_ROWS = OTHER_ROWS + ("wnmf_unit",)
 ADDON_TILTED_ROWS = tuple(r for r in ADDON_ROWS if ROWS[r]["call"] in ("lnmf", "constrainednmf", "cmfwisa"))
 # the all-zero row and column of V, euclidean: the reference stays finite on every add-on call that has a euclidean cost (lnmf has none)
 ADDON_ROWCOL_ROWS = tuple(r for r in ADDON_ROWS if ROWS[r]["call"] != "lnmf")
-EXTRAS = {"constrainednmf": ("Z",), "cmfwisa": ("P", "V_hat")}      # what an add-on call returns besides W, H and the cost
+# the second extension: (row, family) pairs added behind the alpha-beta cases -- every family on the calls that ran `scaled` alone or nearly so
+MORE_FAMILIES = tuple((r, f) for r, fs in (("cnmf_batch", ("tilted", "zeros_v", "zeros_wh")), ("wnmf_batch_mask", ("tilted",)), ("wnmf_batch_weights", ("tilted",)),
+                                           ("wnmf_unit", ("tilted", "zeros_wh")), ("wnmf_random", ("tilted", "zeros_v", "zeros_wh")),
+                                           ("wcnmf_unit", ("tilted", "zeros_v", "zeros_wh")), ("wcnmf_random", ("tilted", "zeros_v", "zeros_wh")),
+                                           ("wcnmf_batch_mask", ("tilted", "zeros_v", "zeros_wh")), ("wcnmf_batch_weights", ("tilted", "zeros_v", "zeros_wh")),
+                                           ("seminmf_k8", ("tilted", "zeros_v")), ("seminmf_k20", ("tilted", "zeros_v"))) for f in fs)
+# LEFT OUT, the float64 reference being non-finite: (seminmf_k8, zeros_h) and (seminmf_k20, zeros_h).  With 40 % exact zeros in H_init the rule
+# H .* sqrt((B+ + C- * H) ./ (B- + C+ * H)) meets entries H(k, j) = 0 whose denominator is exactly 0 as well -- B(k, j) > 0 and C(k, l) <= 0 for every l with H(l, j) > 0;
+# C+(k, k) > 0 does not help, it multiplies the zero itself -- so 0 * sqrt(x / 0) = NaN in the first H step, and tests/seminmf_oracle.py raises at the Cholesky
+# factor of the second iteration (tests/test_regime_inputs_host.py::test_seminmf_zeros_h_has_no_finite_reference).  seminmf_problem still builds the family for that test
+LEFT_OUT = (("seminmf_k8", "zeros_h"), ("seminmf_k20", "zeros_h"))
+EXTRAS = {"constrainednmf": ("Z",), "cmfwisa": ("P", "V_hat"), "seminmf": ("WH",)}      # what an add-on call returns besides W, H and the cost
 
 
 # ---- the alpha-beta divergence: further values of the `div` element of a case, on the nmf and cnmf rows (the batch and weighted calls have none) ---------------
@@ -284,7 +330,7 @@ def shapes(row, family="scaled"):
 def key(row):
     """what the reference of a row depends on (rows that differ in the path alone share it): the keys of SCALED_P and TILT_RATIO"""
     r = ROWS[row]
-    call = {"nmf_batch": "nmfbatch", "cnmf_batch": "cnmfbatch", "wnmf_batch": "wnmfbatch"}.get(r["call"], r["call"])
+    call = {"nmf_batch": "nmfbatch", "cnmf_batch": "cnmfbatch", "wnmf_batch": "wnmfbatch", "wcnmf_batch": "wcnmfbatch"}.get(r["call"], r["call"])
     more = ([r["weights"]] if r.get("weights") else []) + (["+".join(str(k) for k in r["Ks"])] if "Ks" in r else []) + (["sW%g_sH%g" % r["sc"]] if "sc" in r else [])
     return "_".join([call, "x".join(str(d) for d in r["shape"])] + more)
 
@@ -295,7 +341,7 @@ def weights(row, family="scaled"):
     kind = ROWS[row].get("weights")
     if kind is None:
         return None
-    if ROWS[row]["call"] == "wnmf_batch":
+    if ROWS[row]["call"] in ("wnmf_batch", "wcnmf_batch"):      # tests/wcnmf_batch_inputs.py::weights is wnmf_batch_inputs' own
         import wnmf_batch_inputs as WB
         return [WB.weights(b, m, n, kind) for b, (m, n, K, T) in enumerate(shapes(row, family))]
     m, n = ROWS[row]["shape"][:2]
@@ -376,6 +422,11 @@ SCALED_P = {
     ("wnmfbatch_70x5_mask", "kl"): (-53, -63),
     ("wnmfbatch_70x5_weights", "euclidean"): (-25, -31),
     ("wnmfbatch_70x5_weights", "kl"): (-52, -63),
+    # wcnmf_batch: as cnmf_batch under its weights (the floor of 4 % under the fractions are the time slices t >= n_b of the problem with n_b = 2: denominators of exactly 0)
+    ("wcnmfbatch_70x5x3_mask", "euclidean"): (-26, -32),
+    ("wcnmfbatch_70x5x3_mask", "kl"): (-52, -63),
+    ("wcnmfbatch_70x5x3_weights", "euclidean"): (-25, -32),
+    ("wcnmfbatch_70x5x3_weights", "kl"): (-52, -63),
 }
 
 
@@ -389,8 +440,14 @@ IS_HGUARD_P = 57
 
 # wnmf_batch is float64 throughout (only V and the weights are fp32 values), so the euclidean H-step denominator W' * (M .* V_hat) can be taken below eps with nothing
 # leaving a number format: the largest p at which the H-step guard of nb_pass.h replaces 10-90 % of the denominators (pooled over the batch) in some iteration, without lambda
-# (`hmixed`) and with lambda = 2^-54 (`hsparse`: pos + lambda < eps) alike
-BATCH_HGUARD_P = {("wnmfbatch_70x5_mask", "euclidean"): -52, ("wnmfbatch_70x5_weights", "euclidean"): -52}
+# (`hmixed`) and with lambda = 2^-54 (`hsparse`: pos + lambda < eps) alike.  The same holds for nmf_batch, cnmf_batch and wcnmf_batch (nb_pass.h as compiled into
+# nmf_batch.hip, the H updates of cnmf_batch.hip and wcnmf_batch.hip): p = -53 for nmf_batch, where the fraction goes from 0.07 to 0.72 within a binade, -51 ... -53 on the
+# convolutive ones, whose short problems reach the guard first.  The W step is clamped throughout at these p
+BATCH_HGUARD_P = {("wnmfbatch_70x5_mask", "euclidean"): -52, ("wnmfbatch_70x5_weights", "euclidean"): -52,
+                  ("nmfbatch_70x5", "euclidean"): -53, ("cnmfbatch_70x5x3", "euclidean"): -53,
+                  ("wcnmfbatch_70x5x3_mask", "euclidean"): -51, ("wcnmfbatch_70x5x3_weights", "euclidean"): -53}
+# the same for the float64 mode of nmf (csrc/nmf64.hip keeps V, W, H and every contraction in float64), by ROW: the fp32 rows of the same shape share its key
+F64_HGUARD_P = {("nmf_f64", "euclidean"): -53}
 
 
 # The scaled exponents of the alpha-beta cases per (key(row), pair), from regime_oracle._ab_iterations (the float64 restatement with `pos` taken after the outer
@@ -449,6 +506,17 @@ AB_P = {
 }
 
 
+# seminmf: the largest |p| of either sign at which everything csrc/seminmf.hip holds in fp32 -- V, the images of W and H, B = W' * V -- stays a normal fp32 number with the
+# factor 2^20 to spare, from regime_oracle._seminmf_iterations; pinned by tests/test_regime_inputs_host.py::test_seminmf_range_tags_are_the_largest_inside_fp32
+# (the lower end is set by the smallest entry of the mixed-sign B, a near-cancellation at 2^-14 of the typical one; the upper end by its largest)
+SEMI_P = {"seminmf_96x300x8": (-46, 51), "seminmf_128x400x20": (-42, 51)}
+# its `sens`: (W, H and W * H; cost), the largest over the cases of the row, under a relative nudge of +-2^-24 of W_init and H_init -- the inits are fp32 values already, so
+# the nudge stands for the rounding, as in tests/golden/make_seminmf_golden.py.  The bar is max(contract, 2 * sens), as in tests/test_gpu_seminmf.py
+# NOTE: on the tilted case of either row the cost moves by 5.9e-8 / 5.7e-8, above a twentieth of its contract (5e-8) though 2 * sens stays eight times below the bar;
+# every other figure is below a twentieth.  The inputs are kept as they are
+SEMI_SENS = {"seminmf_96x300x8": (2.3e-7, 5.9e-8), "seminmf_128x400x20": (2.4e-7, 5.7e-8)}
+
+
 # `sens` per key: the largest movement of the float64 reference, over the cases of the key, when W_init and H_init are rounded to fp32 once -- (on W, H and the further
 # outputs; on the cost).  nmfsc, cnmfsc and cmfwisa allow max(contract, 2 * sens) in their own files; every figure here is below a twentieth of the contract, so the
 # contract alone is the bar of these rows.  Computed and pinned by tests/test_regime_inputs_host.py::test_reference_sensitivity (within a factor 2)
@@ -469,6 +537,9 @@ SENS = {
 def scaled_tags(row, div):
     """the scaled cases of (row, div): tag -> (p, lambda)"""
     call = ROWS[row]["call"]
+    if call == "seminmf":      # no guard: the range alone
+        lo, hi = SEMI_P[key(row)]
+        return {"m%d" % -lo: (lo, 0.0), "p%d" % hi: (hi, 0.0)}
     if div in AB:
         ps = AB_P[(key(row), div)]
         tags = {t: (ps[t], 0.0) for t in ("mixed", "clamped") if t in ps}
@@ -490,9 +561,19 @@ def scaled_tags(row, div):
         return {"m40": (-40, 0.0), "p40": (40, 0.0), "hguard": (IS_HGUARD_P, 0.0), "hsparse": (IS_HGUARD_P, LAMBDA)}
     mixed, clamped = SCALED_P[(key(row), div)]
     tags = {"mixed": (mixed, 0.0), "clamped": (clamped, 0.0), "p40": (40, 0.0), "sparse": (mixed, LAMBDA)}
-    if (key(row), div) in BATCH_HGUARD_P:
-        tags.update(hmixed=(BATCH_HGUARD_P[(key(row), div)], 0.0), hsparse=(BATCH_HGUARD_P[(key(row), div)], LAMBDA))
+    hp = F64_HGUARD_P.get((row, div), BATCH_HGUARD_P.get((key(row), div)))
+    if hp is not None:
+        tags.update(hmixed=(hp, 0.0), hsparse=(hp, LAMBDA))
     return tags
+
+
+def second_extension(row, family, div, tag):
+    """whether a case belongs to the second extension of the table: cases() keeps those behind every earlier case, whose ids and order stay as they were"""
+    if row in NEW_ROWS:
+        return True
+    if family == "scaled":
+        return tag in ("hmixed", "hsparse") and ((row, div) in F64_HGUARD_P or ROWS[row]["call"] in ("nmf_batch", "cnmf_batch"))
+    return (row, family) in MORE_FAMILIES
 
 
 # ---- tilted: how much more sensitive the reference itself is per row on tilted data ---------------------------------------------------------------------
@@ -570,6 +651,31 @@ TILT_RATIO = {
     ("cnmf_129x333x32x4", "ab_a2_b-0.5"): (2.03, 1.64),
     ("cnmf_129x333x64x2", "ab_a0.5_b1.5"): (4.37, 2.06),
     ("cnmf_129x333x64x2", "ab_a2_b-0.5"): (2.51, 1.64),
+    # the second extension: the weighted rows pass their weights through (regime_oracle.tilt_ratio)
+    ("cnmfbatch_70x5x3", "euclidean"): (3.04, 1.21),
+    ("cnmfbatch_70x5x3", "kl"): (12.1, 1),
+    ("wnmfbatch_70x5_mask", "euclidean"): (14.2, 2.57),
+    ("wnmfbatch_70x5_mask", "kl"): (17.1, 2.19),
+    ("wnmfbatch_70x5_weights", "euclidean"): (11.4, 2.1),
+    ("wnmfbatch_70x5_weights", "kl"): (17.3, 1.97),
+    ("wnmf_129x200x33_unit", "euclidean"): (5.39, 2.28),
+    ("wnmf_129x200x33_unit", "kl"): (14.6, 2.09),
+    ("wnmf_129x200x33_unit", "is"): (8.46, 3.45),
+    ("wnmf_129x200x33_random", "euclidean"): (5.23, 2.07),
+    ("wnmf_129x200x33_random", "kl"): (18.3, 2.27),
+    ("wnmf_129x200x33_random", "is"): (8.68, 3.45),
+    ("wcnmf_70x90x5x4_unit", "euclidean"): (4.24, 2.37),
+    ("wcnmf_70x90x5x4_unit", "kl"): (15.5, 2.23),
+    ("wcnmf_70x90x5x4_unit", "is"): (22, 8.22),
+    ("wcnmf_70x90x5x4_random", "euclidean"): (4.24, 2.19),
+    ("wcnmf_70x90x5x4_random", "kl"): (17.6, 2.05),
+    ("wcnmf_70x90x5x4_random", "is"): (52.4, 11.1),
+    ("wcnmfbatch_70x5x3_mask", "euclidean"): (5.62, 1.72),
+    ("wcnmfbatch_70x5x3_mask", "kl"): (12.3, 1.32),
+    ("wcnmfbatch_70x5x3_weights", "euclidean"): (19.3, 1.55),
+    ("wcnmfbatch_70x5x3_weights", "kl"): (22.9, 2.43),
+    ("seminmf_96x300x8", "euclidean"): (1.97, 2.16),      # (under regime_oracle.nudged_inits: seminmf's inits are fp32 values)
+    ("seminmf_128x400x20", "euclidean"): (1, 1.63),
 }
 
 
@@ -584,6 +690,9 @@ def problems(row, family, div, tag=""):
     """the problems of a case: a list of (V, W_init, H_init), and the sparsity lambda of the case"""
     lam, out = 0.0, []
     addon = ROWS[row]["call"] in ADDON_CALLS
+    if ROWS[row]["call"] == "seminmf":
+        p = scaled_tags(row, div)[tag][0] if family == "scaled" else 0
+        return [seminmf_problem(row, family, p, tag)], 0.0
     for b, (m, n, K, T) in enumerate(shapes(row, family)):
         p = 0
         if family == "scaled":
@@ -600,6 +709,8 @@ def problems(row, family, div, tag=""):
             out.append(zeros_wh(m, n, K, T, b=b))
         else:
             raise ValueError(family)
+    if ROWS[row]["call"] == "wcnmf_batch":      # V is NaN in the holes, as in tests/wcnmf_batch_inputs.py: whatever reads V there shows
+        out = [(np.where(M > 0, V, np.nan), W0, H0) for M, (V, W0, H0) in zip(weights(row, family), out)]
     return out, lam
 
 
@@ -608,7 +719,7 @@ def cases():
     out = []
     for row in SCALED_ROWS:
         for div in ROWS[row]["divs"]:
-            out += [(row, "scaled", div, tag) for tag in scaled_tags(row, div)]
+            out += [(row, "scaled", div, tag) for tag in scaled_tags(row, div) if not second_extension(row, "scaled", div, tag)]
     for row in OTHER_ROWS:
         for div in ROWS[row]["divs"]:
             out += [(row, "tilted", div, ""), (row, "zeros_wh", div, "")]
@@ -627,6 +738,14 @@ def cases():
         for div in ab_divs(row):
             out += [(row, "scaled", div, tag) for tag in scaled_tags(row, div)]
             out += [(row, family, div, "") for family in AB_FAMILIES[div]]
+    for row in ROWS:      # the second extension, behind those again: the hmixed / hsparse cases of the float64 rows, the wcnmf_batch rows, MORE_FAMILIES
+        for div in ROWS[row]["divs"]:
+            out += [(row, "scaled", div, tag) for tag in scaled_tags(row, div) if second_extension(row, "scaled", div, tag)]
+    for row, family in MORE_FAMILIES:
+        for div in ROWS[row]["divs"]:
+            out.append((row, family, div, ""))
+        if family == "zeros_v":
+            out.append((row, family, "euclidean", "rowcol"))
     return out
 
 

@@ -29,6 +29,11 @@ def run_one(row, M, prob, div, lam, trace=None):
         return run_addon(row, prob, div, lam)
     V, W0, H0 = prob
     K = H0.shape[0]
+    if call == "seminmf":      # tests/seminmf_oracle.py, stop rule off; W * H behind the cost (regime_inputs.EXTRAS)
+        import seminmf_oracle as SO
+        assert trace is None and lam == 0.0
+        W, H, c = SO.seminmf(V, K, dict(W_init=W0, H_init=H0, maxiter=R.ITERS, tolerance=-1.0))
+        return W, H, c, W @ H
     cfg = _cfg(div, W0, H0, lam)
     cfg_o = {k: v for k, v in cfg.items() if k != "nmfx_disable_stop"}
     if call in ("nmf", "nmf_batch"):
@@ -44,6 +49,7 @@ def run_one(row, M, prob, div, lam, trace=None):
     if call in ("wnmf", "wnmf_batch"):
         from wnmf_oracle import wnmf
         return wnmf(V, M, K, cfg, trace=trace)
+    assert call in ("wcnmf", "wcnmf_batch"), call      # wcnmf_batch: tests/wcnmf_oracle.py on every problem alone (V may be NaN where M == 0: the maps select on M)
     from wcnmf_oracle import wcnmf
     return wcnmf(V, M, K, W0.shape[2], cfg, trace=trace)
 
@@ -71,7 +77,7 @@ def weights_per_problem(row, family, count):
 
 def reference(row, family, div, tag=""):
     """[(W, H, cost) per problem] of a case (an add-on call: its further outputs behind them, regime_inputs.EXTRAS); rows that differ in the path alone share one run"""
-    first = next(r for r in R.ROWS if R.key(r) == R.key(row))
+    first = next(r for r in R.ROWS if R.key(r) == R.key(row) and (family != "scaled" or tag in R.scaled_tags(r, div)))      # (hmixed / hsparse of nmf_f64: its own)
     return _reference(R.key(row), first, family, div, tag)
 
 
@@ -89,6 +95,9 @@ def iterations(row, M, prob, div, lam):
     denominators the max(pos + lambda, eps) guard replaces, the fraction of the W-step denominators where pos < eps <= pos + lambda, and name -> (smallest non-zero, largest) magnitude (cost_residual: largest, largest) of every intermediate: V, V_hat, the element maps, the
     numerators and denominators of both steps, the update quotients and the per-element cost terms with their total"""
     call = R.ROWS[row]["call"]
+    if call == "seminmf":
+        with np.errstate(all="ignore"):
+            return _seminmf_iterations(row, prob)
     if call in R.ADDON_CALLS and call != "wnmf_batch":
         with np.errstate(all="ignore"):
             return ADDON_ITERATIONS[call](row, prob, div, lam)
@@ -252,12 +261,52 @@ def kappa(row, family, div, tag=""):
     return _kappa(R.key(row), first, family, div, tag)
 
 
+def _seminmf_iterations(row, prob):
+    """seminmf.m:65-89 restated with what csrc/seminmf.hip holds in fp32 kept -- V, the images of W and H, B = W' * V (an fp32 MFMA) --, besides the float64 Gram
+    matrices, the two sums under the square root and the cost; ends where the oracle ends.  There is no guard: the fractions are 0"""
+    import seminmf_oracle as SO
+    V, W0, H = prob
+    out, cost = [], []
+    for it in range(R.ITERS):
+        mags = _Mags()
+        W = SO._solve_right(V @ H.T, H @ H.T, it + 1)
+        B, C = W.T @ V, W.T @ W
+        num, den = np.maximum(B, 0.0) + np.maximum(-C, 0.0) @ H, np.maximum(-B, 0.0) + np.maximum(C, 0.0) @ H
+        H = H * np.sqrt(num / den)
+        for nm, x in (("V", V), ("W", W), ("B", B), ("H", H), ("C", C), ("H_num", num), ("H_den", den)):
+            mags.note(nm, x)
+        cost.append(0.5 * np.sum((V - W @ H) ** 2))
+        mags.note("cost", cost[-1])
+        out.append(dict(guard_W=0.0, guard_H=0.0, lambda_decides=0.0, mags=mags))
+    _ends_where((W, H, cost), run_one(row, None, prob, "euclidean", 0.0)[:3], "seminmf restated")
+    return out
+
+
+def nudged_inits(prob):
+    """seminmf's inits are fp32 values already, so one fp32 rounding is the identity: a relative nudge of +-2^-24 (seeded) stands for it, as in
+    tests/golden/make_seminmf_golden.py"""
+    V, W0, H0 = prob
+    rs = np.random.RandomState(99)
+    nudge = lambda x: x * (1 + 2.0 ** -24 * rs.choice([-1.0, 1.0], size=np.shape(x)))
+    return V, nudge(W0), nudge(H0)
+
+
+def seminmf_sensitivity(row, family, tag=""):
+    """(W, H, cost, W * H): the movement of the seminmf reference of a case under nudged_inits -- relative Frobenius, the cost the largest relative"""
+    (prob,), _ = R.problems(row, family, "euclidean", tag)
+    ref = reference(row, family, "euclidean", tag)[0]
+    with np.errstate(all="ignore"):
+        got = run_one(row, None, nudged_inits(prob), "euclidean", 0.0)
+    return rel(got[0], ref[0]), rel(got[1], ref[1]), float(np.max(np.abs(got[2] - ref[2]) / np.abs(ref[2]))), rel(got[3], ref[3])
+
+
 def row_movement(row, M, prob, div):
     """the reference's own conditioning per row: the largest relative movement of a row of its W (all components and time slices of that row) and of a
     column of its H when W_init and H_init are rounded to fp32 once"""
     with np.errstate(all="ignore"):
         W, H = run_one(row, M, prob, div, 0.0)[:2]
-        W2, H2 = run_one(row, M, rounded_inits(prob), div, 0.0)[:2]
+        moved = nudged_inits(prob) if R.ROWS[row]["call"] == "seminmf" else rounded_inits(prob)
+        W2, H2 = run_one(row, M, moved, div, 0.0)[:2]
     return per_row(W2, W), per_col(H2, H)
 
 
@@ -276,11 +325,10 @@ def per_col(H, H0):
 
 def tilt_ratio(row, div):
     """(rW, rH) of TILT_RATIO: row_movement on tilted data over row_movement on untilted data, the worst problem of a batch on either side, never below 1"""
-    M = R.weights(row)
     mv = {}
     for tag in ("", "flat"):
         probs, _ = R.problems(row, "tilted", div, tag)
-        mv[tag] = np.max([row_movement(row, M, p, div) for p in probs], axis=0)
+        mv[tag] = np.max([row_movement(row, M, p, div) for M, p in zip(weights_per_problem(row, "tilted", len(probs)), probs)], axis=0)
     return max(1.0, mv[""][0] / mv["flat"][0]), max(1.0, mv[""][1] / mv["flat"][1])
 
 

@@ -83,3 +83,37 @@ def ref_estimates(shape, power, dtype, seed=0):
         X = X.astype(np.complex128)
         return [mk * X.real + 1j * (mk * X.imag) for mk in M]
     return [mk * X.astype(np.float64) for mk in M]
+
+
+# ---- the ladder: every source two decades below the one before --------------------------------------------------------------------------------------------
+# H_i = (rand + 0.5) * 10^(-2 i), W as in factors(): the ratios r_i = S_i / S step down by 1e-2 per rung, to 1e-6 with four sources (register form) and
+# 1e-8 with five (sweep form).  A general power r_i .^ p is formed as exp2(p * log2 r_i), whose relative error grows with |p * log2 r_i|: the weak rungs
+# are where it shows, and the bar is held on EVERY source's mask and estimate, not on the worst of a case that the strong sources dominate.
+# tests/test_softmask_host.py asserts that every r_i .^ p of the statement stays at or above 2^-106 (fp32 normal with a factor 2^20 to spare)
+LADDER_SHAPES = [(70, 90, (3,) * 4, 1), (70, 90, (3,) * 4, 4), (70, 90, (3,) * 5, 1), (70, 90, (3,) * 5, 4)]      # register, register, sweep, sweep
+LADDER_POWERS = (3.0, 0.5, 2.0)      # 3 and 0.5: the exp2 / log2 path; 2: the squared ratio
+
+
+@functools.lru_cache(maxsize=None)
+def ladder_factors(shape):
+    """W, H as lists, float64, drawn in the order of factors()"""
+    m, n, Ks, T = shape
+    r = np.random.RandomState(1234)
+    W, H = [], []
+    for i, K in enumerate(Ks):
+        w = r.rand(m, K, T) + 0.01
+        h = (r.rand(K, n) + 0.5) * 10.0 ** (-2 * i)
+        W.append(w[:, :, 0] if T == 1 else w)
+        H.append(h)
+    for a in W + H:
+        a.setflags(write=False)
+    return W, H
+
+
+@functools.lru_cache(maxsize=None)
+def ladder_ref_masks(shape, power):
+    W, H = ladder_factors(shape)
+    M = O.masks(W, H, power)
+    for a in M:
+        a.setflags(write=False)
+    return M

@@ -1,7 +1,8 @@
 """impute / holdout / impute_batch / holdout_batch on the MI355X against the float64 statement tests/impute_oracle.py (cases: tests/impute_inputs.py, whose
 conditioning tests/test_impute_host.py checks).  Bars: the project's contract, 1e-5 relative Frobenius on the filled entries of Y (over the holes only) and
 1e-6 relative on fit and on held.  Measured worst over the cases below: fill 2.5e-7 (200 x 300, K = 256), fit 3.0e-8, held 9.0e-8 (70 x 30, T = 64);
-holdout's fit against the last cost of wnmf / wcnmf 5.2e-9 (profiles/impute_parity_errors.json)."""
+holdout's fit against the last cost of wnmf / wcnmf 5.2e-9; the value-range cases: fill 1.2e-7, worst row 1.6e-7, fit 5.2e-9, held 4.2e-9
+(profiles/impute_parity_errors.json)."""
 import numpy as np
 import pytest
 
@@ -248,3 +249,37 @@ def test_timing_counts_the_bytes(gpu_lib):
     gpu_lib.holdout_batch([V, V[:, :70]], [M, M[:, :70]], [W, W], [H, H[:, :70]])
     t = _lib.last_call_timing()
     assert t["host_bytes_in"] == 2 * 8 * m * (n + 70) + 8 * (2 * m * K * T + K * (n + 70)) and t["host_bytes_out"] == 2 * 2 * 8
+
+
+# ---- value ranges -----------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", I.DTYPES)
+@pytest.mark.parametrize("case", I.REGIME_CASES, ids=I.regime_ident)
+def test_value_ranges(gpu_lib, case, dtype):
+    """impute_inputs.REGIME_CASES (conditioned on the CPU by tests/test_impute_host.py) at the bars of this file.  scaled: V and H times 2^p at the largest |p| of
+    either sign that keeps S, V and the largest cost term inside fp32.  tilted: rows twelve decades apart, the fill judged PER ROW over that row's holes -- the
+    Frobenius norm over all holes is the loud rows'.  zeros_v: 30 % exact zeros in V: impute hands them back bit for bit, kl scores NaN and is +Inf for fit and
+    for held exactly as the statement does, euclidean stays at the bar"""
+    shape, family, p = case
+    V, M, W, H = I.regime_case(shape, family, p)
+    V, M = V.astype(dtype), M.astype(dtype)
+    ref = I.regime_ref(shape, family, p, dtype)
+    on = M > 0
+    Y = gpu_lib.impute(V, M, W, H)
+    scores = {d: gpu_lib.holdout(V, M, W, H, dict(divergence=d)) for d in I.DIVS}
+    assert Y.shape == V.shape and Y.dtype == V.dtype and np.array_equal(_bits(Y)[on], _bits(V)[on]) and np.all(np.isfinite(Y))
+    e = dict(fill=I.hole_error(Y, ref["Y"], M), fill_row=float(I.row_hole_errors(Y, ref["Y"], M).max()))
+    bad = []
+    for d, (fit, held) in scores.items():
+        if np.isfinite(ref[d][0]) and np.isfinite(ref[d][1]):
+            if family != "tilted":
+                e["fit_" + d], e["held_" + d] = I.rel(fit, ref[d][0]), I.rel(held, ref[d][1])
+        elif not np.array_equal((fit, held), ref[d], equal_nan=True):      # the statement's NaN / +Inf, for fit and for held
+            bad.append((d, (fit, held), ref[d]))
+    print(I.regime_ident(case), dtype, e)
+    record_err(**{"regime_" + k.split("_")[0]: v for k, v in e.items() if k != "fill_row"}, regime_fill_row=e["fill_row"])
+    assert not bad, bad
+    assert e["fill"] < I.BAR_FILL and all(v < I.BAR_SCORE for k, v in e.items() if k[:3] in ("fit", "hel")), e
+    if family == "tilted":
+        assert e["fill_row"] < I.BAR_ROW_FILL, e
+    if family == "zeros_v":
+        assert {d for d in I.DIVS if not np.isfinite(ref[d][0])} == {"kl", "is"} and np.isfinite(scores["euclidean"][0])

@@ -22,7 +22,15 @@ the dual form have a +Inf cost in every entry: the same-pattern rule.  The float
 The add-on calls with guard copies of their own -- lnmf, constrainednmf, nmfsc, cnmfsc, cmfwisa, wnmf_batch (regime_inputs.ADDON_ROWS) -- run the same families.  What they return besides
 W, H and the cost (constrainednmf: Z; cmfwisa: P and V_hat, its W and H as the sources side by side) is held to the bar of W and H; a zero of Z_init stays an exact zero of Z.
 nmfsc, cnmfsc and cmfwisa keep the plain contract: tests/test_regime_inputs_host.py pins the movement of their references under one fp32 rounding of the inits
-(regime_inputs.SENS), a twentieth of the contract at most.  wnmf_batch keeps the bars of tests/test_gpu_wnmf_batch.py, imported from there: 1e-9, on the cost relative where n_b > K and against the first cost where n_b <= K."""
+(regime_inputs.SENS), a twentieth of the contract at most.  wnmf_batch keeps the bars of tests/test_gpu_wnmf_batch.py, imported from there: 1e-9, on the cost relative where n_b > K and against the first cost where n_b <= K.
+
+The second extension (regime_inputs.second_extension, 97 cases behind the 791 earlier ones) completes the table.  wcnmf_batch (rows wcnmf_batch_mask / _weights, V NaN in its
+holes) runs all four families at the bars of tests/test_gpu_wcnmf_batch.py, imported from there: 1e-9, the cost relative where n_b > K * T and against the first cost where
+n_b <= K * T.  cnmf_batch, wnmf and wcnmf (unit and random weights) run tilted, zeros_v and zeros_wh as well, wnmf_batch tilted.  The float64 kernels -- the float64 mode of
+nmf, nmf_batch, cnmf_batch, wcnmf_batch -- run `hmixed` / `hsparse` under euclidean: p = -51 ... -53, where their H-step guard replaces 10-90 % of its denominators with
+nothing leaving float64 (regime_inputs.BATCH_HGUARD_P, F64_HGUARD_P).  seminmf (rows seminmf_k8, seminmf_k20; no guard) runs scaled at the largest |p| of either sign that
+keeps V, the fp32 images of W and H and B = W' * V inside fp32, tilted (per row of W, per column of H) and zeros_v, at max(contract, 2 * sens) as in
+tests/test_gpu_seminmf.py, W * H held to the bar of W and H; its zeros_h family has no finite reference and is left out (regime_inputs.LEFT_OUT)."""
 import numpy as np
 import pytest
 
@@ -30,6 +38,7 @@ import regime_inputs as R
 import regime_oracle as RO
 import test_gpu_cnmf_batch as TCB
 import test_gpu_nmf64 as T64
+import test_gpu_wcnmf_batch as TWCB
 import test_gpu_wnmf_batch as TWB
 from conftest import record_err, rel_fro
 
@@ -40,8 +49,13 @@ max_rel = lambda c, c0: float(np.max(np.abs(c - c0) / np.abs(c0)))
 BARS = {"nmf_f64": (T64.TOL_WH, T64.TOL_COST, T64.TOL_COST, max_rel), "nmf_batch": (TCB.TOL, TCB.TOL, TCB.TOL, max_rel),
         "cnmf_batch": (TCB.TOL, TCB.TOL, TCB.TOL, max_rel),
         # wnmf_batch keeps the bars of its own file: 1e-9, on the cost relative where n_b > K and against the first cost where an exact fit exists (n_b <= K)
-        "wnmf_batch_mask": (TWB.TOL, TWB.TOL, TWB.TOL, max_rel), "wnmf_batch_weights": (TWB.TOL, TWB.TOL, TWB.TOL, max_rel)}
-F64_ROWS = ("nmf_f64", "nmf_batch", "cnmf_batch", "wnmf_batch_mask", "wnmf_batch_weights")
+        "wnmf_batch_mask": (TWB.TOL, TWB.TOL, TWB.TOL, max_rel), "wnmf_batch_weights": (TWB.TOL, TWB.TOL, TWB.TOL, max_rel),
+        # wcnmf_batch likewise: 1e-9, the cost relative where n_b > K * T and against the first cost where n_b <= K * T
+        "wcnmf_batch_mask": (TWCB.TOL, TWCB.TOL, TWCB.TOL, max_rel), "wcnmf_batch_weights": (TWCB.TOL, TWCB.TOL, TWCB.TOL, max_rel)}
+# seminmf: max(contract, 2 * sens) as in tests/test_gpu_seminmf.py, the cost by its largest relative error; regime_inputs.SEMI_SENS is pinned on the CPU, and 2 * sens is
+# below the contract on every case, so these are the contract's figures
+BARS.update({r: (max(1e-5, 2 * R.SEMI_SENS[R.key(r)][0]), max(1e-6, 2 * R.SEMI_SENS[R.key(r)][1]), None, max_rel) for r in R.ROWS if R.ROWS[r]["call"] == "seminmf"})
+F64_ROWS = ("nmf_f64", "nmf_batch", "cnmf_batch", "wnmf_batch_mask", "wnmf_batch_weights", "wcnmf_batch_mask", "wcnmf_batch_weights")
 max_abs_first = lambda c, c0: float(np.max(np.abs(c - c0)) / c0[0])
 CONTRACT = (1e-5, 1e-6, 1e-5, rel_fro)
 # the alpha-beta cost is a difference of three sums: 1e-6 where the reference's cancellation kappa (regime_oracle.kappa: the largest of the three sums over
@@ -61,6 +75,13 @@ def _run(lib, row, probs, div, lam, family="scaled"):
     if call == "wnmf_batch":
         cfg.update(W_init=[p[1] for p in probs], H_init=[p[2] for p in probs])
         return list(zip(*lib.wnmf_batch([p[0] for p in probs], R.weights(row, family), probs[0][2].shape[0], cfg)))
+    if call == "seminmf":      # W * H behind the cost, as regime_oracle.run_one returns it
+        V, W0, H0 = probs[0]
+        W, H, c = lib.seminmf(V, H0.shape[0], dict(r["cfg"], W_init=W0, H_init=H0, maxiter=R.ITERS, nmfx_disable_stop=True))
+        return [(W, H, c, np.asarray(W, dtype=np.float64) @ np.asarray(H, dtype=np.float64))]
+    if call == "wcnmf_batch":
+        cfg.update(W_init=[p[1] for p in probs], H_init=[p[2] for p in probs])
+        return list(zip(*lib.wcnmf_batch([p[0] for p in probs], R.weights(row, family), probs[0][2].shape[0], probs[0][1].shape[2], cfg)))
     if call in R.ADDON_CALLS:      # one problem; the outputs in the layout of regime_oracle.run_addon
         V, W0, H0 = probs[0]
         cfg = dict(RO.addon_config(row, div, probs[0], lam), nmfx_disable_stop=True, **r["cfg"])
@@ -118,6 +139,8 @@ def test_regime(gpu_lib, case):
         if np.all(np.isfinite(c0)):
             ce = cost_err
             if R.ROWS[row]["call"] == "wnmf_batch" and probs[b][0].shape[1] <= H0.shape[0]:
+                ce = max_abs_first
+            if R.ROWS[row]["call"] == "wcnmf_batch" and probs[b][0].shape[1] <= H0.shape[0] * W0.shape[2]:
                 ce = max_abs_first
             e.update(rec(cost=ce(c, c0) if np.all(np.isfinite(c)) else np.inf))
         if family == "tilted":

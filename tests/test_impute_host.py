@@ -416,3 +416,62 @@ def test_split_cases_are_the_same_statement():
         Wl, Hl = I.split(shape, W, H)
         assert isinstance(Wl, list) and len(Wl) == 2 and Wl[0].shape[1] + Wl[1].shape[1] == shape[2]
         assert np.allclose(O.total(Wl, Hl), I.ref_total(shape), rtol=1e-13, atol=0)
+
+
+# ---- the value-range cases of tests/test_gpu_impute.py (impute_inputs.REGIME_CASES) ---------------------------------------------------------------------------
+F32_LO, F32_HI = 2.0 ** -106, 2.0 ** 107      # fp32's normal range with a factor 2^20 to spare on either side
+
+
+def _regime_mags(shape, p):
+    """(smallest, largest) magnitude of S, of V, and the largest cost term of every divergence, from the float64 statement"""
+    V, M, W, H = I.regime_case(shape, "scaled", p)
+    S = O.total(W, H)
+    out = dict(S=(S.min(), S.max()), V=(V.min(), V.max()))
+    for d in I.DIVS:
+        t = float(np.abs(O.divergence(d, V, S)).max())
+        out[d] = (t, t)
+    return out
+
+
+@pytest.mark.parametrize("shape", I.REGIME_SHAPES, ids=I.ident)
+def test_regime_exponents_are_the_largest_inside_fp32(shape):
+    inside = lambda p: all(lo >= F32_LO and hi <= F32_HI for lo, hi in _regime_mags(shape, p).values())
+    lo, hi = I.REGIME_P[shape]
+    print(shape, {k: tuple(np.round(np.log2(v), 1)) for p in (lo, hi) for k, v in _regime_mags(shape, p).items()})
+    assert lo < 0 < hi and inside(lo) and inside(hi) and not inside(lo - 1) and not inside(hi + 1)
+
+
+@pytest.mark.parametrize("dtype", I.DTYPES)
+@pytest.mark.parametrize("case", I.REGIME_CASES, ids=I.regime_ident)
+def test_regime_cases_stay_inside_the_bars_with_s_in_float32(case, dtype):
+    """the statement against itself with S formed in float32, as test_cases_stay_inside_the_bars_with_s_in_float32; tilted: on EVERY row's holes, with the
+    rows twelve decades apart; zeros_v: the zeros sit in observed entries and in holes, kl is NaN and is +Inf for fit and for held, euclidean finite"""
+    shape, family, p = case
+    V, M, W, H = I.regime_case(shape, family, p)
+    assert np.array_equal(V, V.astype(np.float32).astype(np.float64)) and np.all(np.isfinite(V)) and np.all(V >= 0)
+    Vt, Mt = I.travelling(V, dtype), I.travelling(M, dtype)
+    on = Mt > 0
+    ref = I.regime_ref(shape, family, p, dtype)
+    S32 = O.total32(W, H)
+    Y32 = O.impute(Vt, Mt, W, H, S=S32)
+    assert np.all(np.isfinite(ref["S"])) and np.all(ref["S"] > 0) and np.all(np.isfinite(S32)) and np.array_equal(Y32[on], Vt[on])
+    e_fill = I.hole_error(Y32, ref["Y"], Mt)
+    rows = I.row_hole_errors(Y32, ref["Y"], Mt)
+    print(I.regime_ident(case), dtype, "fill %.3g worst row %.3g" % (e_fill, rows.max()))
+    assert e_fill < I.BAR_FILL
+    if family == "tilted":
+        Sr = np.linalg.norm(ref["S"], axis=1)
+        assert Sr.max() / Sr.min() > 1e11 and len(rows) == shape[0]      # every row has holes, and the quiet rows are quiet
+        assert rows.max() < I.BAR_ROW_FILL, rows.max()
+    if family == "zeros_v":
+        z = V == 0
+        assert 0.25 < z.mean() < 0.35 and z[on].any() and z[~on].any()
+    for d in I.DIVS:
+        got = O.holdout(Vt, Mt, W, H, d, S=S32)
+        if family == "zeros_v" and d != "euclidean":
+            want = (np.nan, np.nan) if d == "kl" else (np.inf, np.inf)
+            assert np.array_equal(ref[d], want, equal_nan=True) and np.array_equal(got, want, equal_nan=True)
+        elif family != "tilted":      # (tilted: the fill alone is judged; the scores are sums the loud rows own)
+            e = max(I.rel(got[0], ref[d][0]), I.rel(got[1], ref[d][1]))
+            print(d, "%.3g" % e)
+            assert np.isfinite(e) and e < I.BAR_SCORE and ref[d][0] > 0 and ref[d][1] > 0, (d, e)

@@ -3,7 +3,9 @@ tests/regime_inputs.py the reference stays finite and its cost has the expected 
 guard as often as their names say, and everything an fp32 path forms on them is a normal fp32 number with a factor 2^20 to spare; the per-row
 sensitivity ratios of the tilted cases are the constants stored next to the inputs.  For the add-on calls (regime_inputs.ADDON_ROWS) the steps are restated in
 tests/regime_oracle.py with their denominators kept, and every restatement must end where the oracle ends; FP32_HELD names what the device holds in fp32 where a call keeps the
-rest in float64."""
+rest in float64.  The second extension (regime_inputs.second_extension) brings its own conditions: the euclidean H-step guard fractions of the float64 rows, V NaN in the
+holes of wcnmf_batch and nowhere else, the zero fractions of the short convolutive problems judged over the batch, seminmf's range exponents and sensitivity, and the reason its
+zeros_h family is left out."""
 import re
 
 import numpy as np
@@ -17,7 +19,18 @@ F32_MIN, F32_MAX = 2.0 ** -126, 2.0 ** 127
 # what the device holds in fp32 where a call keeps the rest in float64 (None, the default: everything noted).  cmfwisa: V, S_i = W_i * H_i (an fp32 MFMA on the
 # fp32 images of W and H), A_i = |V_bar_i| ./ beta_i and the numerators A_i * H_i', W_i' * A_i; the denominators, the updates and the cost are float64
 # (csrc/cmfwisa.hip).  wnmf_batch: V and the weights alone (every contraction and every update of csrc/wnmf_batch.hip is float64)
-FP32_HELD = {"cmfwisa": ("V", "S_i", "A", "W_num", "H_num", "H"), "wnmf_batch": ("V",)}
+# seminmf: V, the fp32 images of W and H and B = W' * V (an fp32 MFMA); the Gram matrices, the Cholesky factor, the sums under the square root and the cost are float64
+FP32_HELD = {"cmfwisa": ("V", "S_i", "A", "W_num", "H_num", "H"), "wnmf_batch": ("V",), "wcnmf_batch": ("V",), "seminmf": ("V", "W", "B", "H")}
+# the euclidean H-step guard cases of the float64 rows (regime_inputs.BATCH_HGUARD_P / F64_HGUARD_P): csrc/nb_pass.h, csrc/cnmf_batch.hip and csrc/nmf64.hip keep every
+# contraction, both updates and the cost in float64, V alone may be an fp32 value.  The other cases of these rows stay under the full condition they were written for
+F64_HGUARD_TAGS = ("hmixed", "hsparse")
+
+
+def _held(case):
+    row, _, div, tag = case
+    if tag in F64_HGUARD_TAGS and ((row, div) in R.F64_HGUARD_P or R.ROWS[row]["call"] in ("nmf_batch", "cnmf_batch")):
+        return ("V",)
+    return FP32_HELD.get(R.ROWS[row]["call"])
 
 
 def _unique(cases):
@@ -38,15 +51,28 @@ SCALED = [c for c in CASES if c[1] == "scaled"]
 def test_every_row_of_the_table_is_covered():
     rows = {c[0] for c in R.cases() if c[1] == "scaled"}
     assert rows == set(R.ROWS)
-    assert {c[0] for c in R.cases() if c[1] == "tilted"} == set(R.OTHER_ROWS + R.ADDON_TILTED_ROWS)
-    assert {c[0] for c in R.cases() if c[1] == "zeros_wh"} == set(R.OTHER_ROWS + R.ADDON_ROWS)
-    assert {c[0] for c in R.cases() if c[1] == "zeros_v"} == set(R.ZEROS_V_ROWS + R.ADDON_ROWS)
+    more = lambda f: tuple(r for r, g in R.MORE_FAMILIES if g == f)
+    assert {c[0] for c in R.cases() if c[1] == "tilted"} == set(R.OTHER_ROWS + R.ADDON_TILTED_ROWS + more("tilted"))
+    assert {c[0] for c in R.cases() if c[1] == "zeros_wh"} == set(R.OTHER_ROWS + R.ADDON_ROWS + more("zeros_wh"))
+    assert {c[0] for c in R.cases() if c[1] == "zeros_v"} == set(R.ZEROS_V_ROWS + R.ADDON_ROWS + more("zeros_v"))
+    # the second extension: behind every earlier case; after it every call whose reference is finite there runs all four families, and every float64 row has
+    # the euclidean H-step guard cases
+    new = [c for c in R.cases() if R.second_extension(*c)]
+    assert R.cases()[-len(new):] == new and len(R.cases()) - len(new) == 791
+    everywhere = [r for r in R.ROWS if R.ROWS[r]["call"] in ("nmf", "cnmf", "nmf_batch", "cnmf_batch", "wnmf", "wcnmf", "wnmf_batch", "wcnmf_batch")]
+    for f in ("scaled", "tilted", "zeros_v", "zeros_wh"):
+        assert set(everywhere) <= {c[0] for c in R.cases() if c[1] == f}, f
+    for r in everywhere:
+        assert (r, "zeros_v", "euclidean", "rowcol") in R.cases(), r
+    f64 = [r for r in R.ROWS if r == "nmf_f64" or R.ROWS[r]["call"] in ("nmf_batch", "cnmf_batch", "wnmf_batch", "wcnmf_batch")]
+    for r in f64:
+        assert {(r, "scaled", "euclidean", "hmixed"), (r, "scaled", "euclidean", "hsparse")} <= set(R.cases()), r
     assert {R.ROWS[r]["call"] for r in R.ADDON_ROWS} == set(R.ADDON_CALLS)
     assert len(R.cases()) == len(set(R.cases()))
     # the alpha-beta cases: every nmf and cnmf row, behind the others; (0.5, 1.5) in every family, (2, -0.5) scaled and tilted, (0.5, 0.5) scaled and zeros_wh,
     # (1.5, -1.5) and the dual form scaled on one row per path class
     ab = [c for c in R.cases() if R.ab_pair(c[2]) is not None]
-    assert R.cases()[-len(ab):] == ab and {R.ROWS[r]["call"] for r in R.AB_ROWS} == {"nmf", "cnmf"} and len(R.AB_ROWS) == 14
+    assert R.cases()[791 - len(ab):791] == ab and {R.ROWS[r]["call"] for r in R.AB_ROWS} == {"nmf", "cnmf"} and len(R.AB_ROWS) == 14
     fam = lambda div: {(c[0], c[1]) for c in ab if c[2] == div}
     assert fam("ab_a0.5_b1.5") == {(r, f) for r in R.AB_ROWS for f in ("scaled", "tilted", "zeros_v", "zeros_wh")}
     assert fam("ab_a2_b-0.5") == {(r, f) for r in R.AB_ROWS for f in ("scaled", "tilted")}
@@ -63,9 +89,18 @@ def test_reference_is_finite_with_the_expected_cost_pattern(case):
     probs, _ = R.problems(row, family, div, tag)
     refs = RO.reference(row, family, div, tag)
     assert len(refs) == len(probs)
-    for (V, W0, H0), ref in zip(probs, refs):
+    Ms = RO.weights_per_problem(row, family, len(probs))
+    pooled = []      # the zero counts of the short problems, judged over the batch below
+    for (V, W0, H0), ref, M in zip(probs, refs, Ms):
         W, H, c = ref[:3]
-        assert np.array_equal(V, V.astype(np.complex64 if np.iscomplexobj(V) else np.float32).astype(V.dtype))          # the device's fp32 copy of V is lossless
+        # the short problems (n_b = 2, 3, 5) of the convolutive batches: a seeded fraction means nothing on ten entries, and they do have all-zero rows of M .* V.  The
+        # convolutive reference stays finite on them -- W and H below, under kl too: the term W_t .* cs(W_t .* P_t) keeps the numerator of such a row positive --
+        # so they run as they are, no n_b is swapped; their zero fractions are asserted over the whole batch
+        short = R.ROWS[row]["call"] in ("cnmf_batch", "wcnmf_batch") and V.shape[1] < 16
+        on = np.ones(V.shape, dtype=bool) if M is None else M > 0      # a weighted row: what follows speaks of the observed entries
+        if R.ROWS[row]["call"] == "wcnmf_batch":                       # V is NaN in every hole and nowhere else
+            assert np.array_equal(np.isnan(V), ~on) and (~on).any()
+        assert np.array_equal(V[on], V[on].astype(np.complex64 if np.iscomplexobj(V) else np.float32).astype(V.dtype))          # the device's fp32 copy of V is lossless
         # (nmfsc with a sparse W ends its first W line search by step-size underflow, nmfsc.m:221-225, on every input here: the H of that one step and one cost come back)
         assert np.all(np.isfinite(W)) and np.all(np.isfinite(H)) and len(c) == (1 if R.ROWS[row].get("sc") == (0.4, 0.0) else R.iters(div) + ("sc" in R.ROWS[row]))
         assert len(ref) == 3 + len(R.EXTRAS.get(R.ROWS[row]["call"], ())) and all(np.all(np.isfinite(x)) for x in ref[3:])      # Z; P and V_hat
@@ -83,24 +118,46 @@ def test_reference_is_finite_with_the_expected_cost_pattern(case):
             assert np.all(np.isfinite(c)) and np.all(c > 0)
         if family == "zeros_v":
             z = V == 0
-            assert 0.25 < z.mean() < 0.40
-            if tag == "rowcol":
-                assert np.count_nonzero(z.all(axis=1)) == 1 and np.count_nonzero(z.all(axis=0)) == 1
+            if short:
+                pooled.append((z[on].sum(), on.sum()))
+                assert z[on].any() and not z[on].all()
+                if tag == "rowcol":
+                    assert (z | ~on)[V.shape[0] // 3, :].all() and (z | ~on)[:, V.shape[1] // 2].all()
             else:
+                assert 0.25 < z[on].mean() < 0.40
+            if short:
+                pass
+            elif tag == "rowcol" and R.ROWS[row]["call"] == "wcnmf_batch":      # V is NaN in the holes there
+                assert np.count_nonzero((z | ~on).all(axis=1)) == 1 and np.count_nonzero((z | ~on).all(axis=0)) == 1
+            elif tag == "rowcol":
+                assert np.count_nonzero(z.all(axis=1)) == 1 and np.count_nonzero(z.all(axis=0)) == 1
+            elif M is None or M.all():
                 assert not z.all(axis=1).any() and not z.all(axis=0).any()
+            else:      # zero weights as well: no row and no column of M .* V is all zero
+                assert not (z | ~on).all(axis=1).any() and not (z | ~on).all(axis=0).any()
         if family == "zeros_wh":
             zw, zh = W0 == 0, H0 == 0
             lo = 0.25
             if R.ROWS[row]["call"] == "cmfwisa":      # cmfwisa keeps the first component of EVERY source positive: 0.4 * (1 - I / K_all) expected, 0.257 with five sources of 14
                 Ks = R.ROWS[row]["Ks"]
                 lo = 0.9 * 0.4 * (1 - len(Ks) / sum(Ks))
-            assert lo < zw.mean() < 0.45 and lo < zh.mean() < 0.45
+            if short:
+                pooled.append((zw.sum() + zh.sum(), zw.size + zh.size))
+                assert zw.any() and zh.any()
+            else:
+                assert lo < zw.mean() < 0.45 and lo < zh.mean() < 0.45
             assert not zw.reshape(zw.shape[0], zw.shape[1], -1).all(axis=(0, 2)).any() and not zh.all(axis=1).any()
             Hz = ref[3] if R.ROWS[row]["call"] == "constrainednmf" else H           # constrainednmf: H0 is Z_init, and H = Z * A repeats the columns of Z
             sW, sH = R.ROWS[row].get("sc", (0, 0))                                  # nmfsc / cnmfsc: a projected factor keeps no zero pattern, the multiplicative one does
+            if short:      # n_b < T: the slices t >= n_b meet no column of H, their numerators are exactly 0 and the reference zeroes them; under a mask a row of a late
+                assert not np.any(W[:, :, V.shape[1]:]) and np.all((W == 0)[zw])      # slice may see masked columns alone.  Zeros are made there, none is lost
+                zw = W == 0
             assert (sW > 0 or np.array_equal(np.asarray(W).reshape(W0.shape) == 0, zw)) and (sH > 0 or np.array_equal(Hz == 0, zh))      # a multiplicative update keeps every zero, and makes none (lnmf: through its square root)
-        if family == "tilted":
-            assert np.abs(V).max() / np.abs(V)[V != 0].min() > 1e12
+        if family == "tilted" and not (short and M is not None):      # (under a mask a 70 x 2 problem may miss its corner rows)
+            assert np.abs(V[on]).max() / np.abs(V[on])[V[on] != 0].min() > 1e12
+    if pooled:
+        frac = sum(a for a, _ in pooled) / sum(b for _, b in pooled)
+        assert 0.25 < frac < (0.40 if tag != "rowcol" else 0.55), frac      # rowcol: half of a 70 x 2 problem is its zero column
 
 
 def _iterations(case):
@@ -115,7 +172,7 @@ def test_scaled_guard_fractions(case):
     its, lam = _iterations(case)
     r = R.ROWS[case[0]]
     which = "guard_H" if (r["call"] == "cmfwisa" and case[3] in ("hmixed", "sparse")) or r.get("guard") == "H" else "guard_W"      # cmfwisa: lambda sits in the H-step guard
-    if r["call"] == "wnmf_batch" and case[3] in ("hmixed", "hsparse"):           # the H-step copy of the batch pass: the W step is clamped throughout there
+    if _held(case) == ("V",) and case[3] in ("hmixed", "hsparse"):               # the H-step copies of the float64 rows: the W step is clamped throughout there
         gh = np.array([[i["guard_H"] for i in prob] for prob in its]).mean(axis=0)
         print(case, np.round(gh, 3))
         assert np.any((gh >= 0.10) & (gh <= 0.90)) and lam == (R.LAMBDA if case[3] == "hsparse" else 0.0), gh
@@ -160,7 +217,7 @@ def test_scaled_stays_inside_fp32(case):
     """V, V_hat, the element maps, the numerators, denominators and quotients of both steps, the per-element cost terms (squares included) and the cost:
     normal fp32 numbers with a factor 2^20 to spare on either side"""
     its, _ = _iterations(case)
-    held = FP32_HELD.get(R.ROWS[case[0]]["call"])
+    held = _held(case)
     for prob in its:
         for i in prob:
             assert held is None or set(held) <= set(i["mags"])
@@ -273,7 +330,57 @@ def test_scaled_range_that_is_certified():
     """the range README and DESIGN state: the smallest and the largest exponent any scaled case uses"""
     ps = [R.scaled_tags(c[0], c[2])[c[3]][0] for c in SCALED]
     assert (min(ps), max(ps)) == (-63, 57)
-    assert max(R.scaled_tags(c[0], c[2])[c[3]][0] for c in SCALED if c[2] != "is") == 40 and min(R.scaled_tags(c[0], c[2])[c[3]][0] for c in SCALED if c[2] == "is") == -40
+    assert max(R.scaled_tags(c[0], c[2])[c[3]][0] for c in SCALED if c[2] != "is" and R.ROWS[c[0]]["call"] != "seminmf") == 40      # (seminmf: its own range, SEMI_P)
+    assert max(p for _, p in R.SEMI_P.values()) == 51 and min(R.scaled_tags(c[0], c[2])[c[3]][0] for c in SCALED if c[2] == "is") == -40
+
+
+SEMI_ROWS = [r for r in R.ROWS if R.ROWS[r]["call"] == "seminmf"]
+
+
+@pytest.mark.parametrize("row", SEMI_ROWS)
+def test_seminmf_range_tags_are_the_largest_inside_fp32(row):
+    """regime_inputs.SEMI_P: one binade further, of either sign, and something csrc/seminmf.hip holds in fp32 leaves the 2^20 margin of test_scaled_stays_inside_fp32"""
+    def outside(p):
+        its = RO.iterations(row, None, R.seminmf_problem(row, "scaled", p), "euclidean", 0.0)
+        return [(k, np.log2(i["mags"][k][0]), np.log2(i["mags"][k][1])) for i in its for k in FP32_HELD["seminmf"]
+                if not (i["mags"][k][0] >= F32_MIN * SPARE and i["mags"][k][1] <= F32_MAX / SPARE)]
+    lo, hi = R.SEMI_P[R.key(row)]
+    print(row, outside(lo - 1)[:1], outside(hi + 1)[:1])
+    assert lo < 0 < hi and not outside(lo) and not outside(hi) and outside(lo - 1) and outside(hi + 1)
+    assert set(R.scaled_tags(row, "euclidean")) == {"m%d" % -lo, "p%d" % hi}
+
+
+@pytest.mark.parametrize("row", SEMI_ROWS)
+def test_seminmf_reference_sensitivity(row):
+    """regime_inputs.SEMI_SENS, pinned within a factor 2: the movement of the reference under regime_oracle.nudged_inits, the largest over the cases of the row; below the
+    1e-3 past which a case compares nothing, and 2 * sens below the contract, so that max(contract, 2 * sens) is the contract on every case"""
+    sens = np.array([RO.seminmf_sensitivity(c[0], c[1], c[3]) for c in R.cases() if c[0] == row])
+    got = (float(np.delete(sens, 2, axis=1).max()), float(sens[:, 2].max()))
+    want = R.SEMI_SENS[R.key(row)]
+    print(row, got, want)
+    for g, w in zip(got, want):
+        assert w / 2 <= g <= 1.05 * w, (got, want)
+    assert 2 * want[0] < 1e-5 and 2 * want[1] < 1e-6
+
+
+@pytest.mark.parametrize("row", SEMI_ROWS)
+def test_seminmf_zeros_h_has_no_finite_reference(row):
+    """why regime_inputs.LEFT_OUT names (row, zeros_h): with 40 % exact zeros in H_init the first H step of the float64 statement forms 0 * sqrt(x / 0) = NaN -- entries
+    with H = 0, a positive numerator and a denominator of exactly 0 --, and the oracle refuses the second iteration's H * H'"""
+    import seminmf_oracle as SO
+    assert (row, "zeros_h") in R.LEFT_OUT and not any(c[0] == row and c[1] == "zeros_h" for c in R.cases())
+    V, W0, H0 = R.seminmf_problem(row, "zeros_h")
+    z = H0 == 0
+    assert 0.3 < z.mean() < 0.45 and not z.all(axis=1).any() and not z.all(axis=0).any()
+    W = SO._solve_right(V @ H0.T, H0 @ H0.T, 1)
+    B, C = W.T @ V, W.T @ W
+    num, den = np.maximum(B, 0.0) + np.maximum(-C, 0.0) @ H0, np.maximum(-B, 0.0) + np.maximum(C, 0.0) @ H0
+    bad = z & (den == 0) & (num > 0)
+    print(row, int(bad.sum()), "of", int(z.sum()), "zeros")
+    with np.errstate(all="ignore"):
+        assert bad.any() and np.isnan((H0 * np.sqrt(num / den))[bad]).all()
+        with pytest.raises(SO.SeminmfError):
+            RO.run_one(row, None, (V, W0, H0), "euclidean", 0.0)
 
 
 TILT_KEYS = _unique([c for c in R.cases() if c[1] == "tilted"])

@@ -327,3 +327,26 @@ def test_batch_concatenation_with_zero_halo_columns(monkeypatch, T, output):
             assert len(res) == 2 and all(y.shape == (m, ns[b]) for y in res)
             for y, yr in zip(res, ref):
                 assert np.allclose(y, yr, rtol=1e-12, atol=0)
+
+
+# ---- the ladder case of tests/test_gpu_softmask.py --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("power", I.LADDER_POWERS)
+@pytest.mark.parametrize("shape", I.LADDER_SHAPES, ids=I.ident)
+def test_ladder_stays_inside_fp32(shape, power):
+    """every r_i = S_i / S of the statement steps down by about 1e-2 per rung, and every r_i .^ p is a normal fp32 number with a factor 2^20 to spare (2^-106):
+    the weak rungs are small, not lost.  The masks are fractions that add up to 1, and the weakest one is a real quantity: every entry positive"""
+    W, H = I.ladder_factors(shape)
+    S_i = [O.reconstruct(w, h) for w, h in zip(W, H)]
+    S = sum(S_i)
+    assert np.all(S > 0)
+    r = [s / S for s in S_i]
+    for i in range(1, len(r)):
+        step = np.median(r[i] / r[i - 1])
+        assert 1e-3 < step < 1e-1, (i, step)
+    lo = min(float(np.min(x ** power)) for x in r)
+    print(shape, power, np.log2(lo))
+    assert lo >= 2.0 ** -106
+    M = I.ladder_ref_masks(shape, power)
+    assert np.max(np.abs(sum(M) - 1.0)) < 1e-14 and all(np.all(mk > 0) for mk in M)
+    # the rungs are far apart in the masks too: about 10^(-2 p) per rung
+    assert np.median(M[-1]) < 10.0 ** (-1.5 * power * (len(M) - 1))
