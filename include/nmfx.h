@@ -422,6 +422,27 @@ typedef struct {
 nmfx_status nmfx_engine_workspace_bytes(const nmfx_engine_desc *d, size_t *bytes);
 /* number of fp32 elements of the packed all-reduce buffer [N | P-or-rowsum | ...] */
 nmfx_status nmfx_engine_packed_count(const nmfx_engine_desc *d, size_t *count);
+/* Which kernels an engine of this descriptor would run, read-only and host-only like the two queries above (no device call, nothing allocated): out[i]
+ * for the indices below, capacity >= NMFX_PLAN_COUNT (fewer: NMFX_ERR_INVALID); a descriptor nmfx_engine_create would refuse is refused here with the same
+ * status.  The split factors are the grid.y of the fused passes, chosen from the shape alone: 1 = the pass writes its result in place, > 1 = into that
+ * many slabs that a second kernel sums.  The step and this query decide through the same predicates.  use_vt is what the descriptor asks for; an engine
+ * created on a workspace too small for the transposed copy of V runs without it.  A new entry point; no structure grows, so NMFX_VERSION stays 600. */
+enum {
+    NMFX_PLAN_FUSED = 0,                /* nmf / lnmf / constrainednmf on the register-stationary kernels */
+    NMFX_PLAN_USE_VT = 1,               /* ... with a transposed copy of V in the workspace */
+    NMFX_PLAN_NSPLIT_W = 2,             /* W-step pass: splits over the columns (1 when not fused) */
+    NMFX_PLAN_ISPLIT_H = 3,             /* H-step pass: splits over the rows (1 when not fused) */
+    NMFX_PLAN_NSPLIT_T = 4,             /* cnmf shift-sum passes and the K > 256 column-block passes: splits over the columns (0: neither runs) */
+    NMFX_PLAN_KLW_HSPLIT = 5,           /* K > 256 column-block H-step passes: splits over the rows (0: they do not run) */
+    NMFX_PLAN_DUAL = 6,                 /* is / alpha-beta on the fused kernels: two element maps */
+    NMFX_PLAN_DUAL2 = 7,                /* ... as two single-map passes (K > 192, and the dual form alpha == 0) */
+    NMFX_PLAN_H_UPDATE_IN_EPILOGUE = 8, /* the fused H-step kernel updates H (float64 master and fp32 image) in its own epilogue */
+    NMFX_PLAN_HUG = 9,                  /* euclidean: the H update in Gram form, never in the epilogue */
+    NMFX_PLAN_FUSED_T = 10,             /* cnmf on the fused shift-sum passes */
+    NMFX_PLAN_KLW = 11,                 /* kl with 256 < K <= 2048 on column blocks */
+    NMFX_PLAN_COUNT = 12
+};
+nmfx_status nmfx_engine_plan(const nmfx_engine_desc *d, int32_t *out, int32_t capacity);
 /* V, W, H, workspace, packed: DEVICE pointers owned by the caller; W and H are updated in place */
 nmfx_status nmfx_engine_create(const nmfx_engine_desc *d, const float *V, float *W, float *H, void *workspace,
                                size_t workspace_bytes, float *packed, nmfx_engine **out);

@@ -28,7 +28,7 @@ EXPORTS = [
     "nmfx_engine_set_constraint", "nmfx_nmfsc_dev", "nmfx_engine_wstep_partial_chunk", "nmfx_engine_packed_chunk",
     "nmfx_engine_between_allreduces", "nmfx_engine_between_allreduces_cost", "nmfx_projfunc_dev", "nmfx_nmfsc_profile", "nmfx_nmfsc_profile_ntags", "nmfx_nmfsc_profile_tag_name", "nmfx_nmfsc_profile_read", "nmfx_last_call_timing", "nmfx_sc_iteration_seconds", "nmfx_engine_cost_lag", "nmfx_engine_sumvv_local", "nmfx_engine_sumvv_set_global",
     "nmfx_minmax_dev", "nmfx_scale_dev", "nmfx_gemm64", "nmfx_engine_sync_master", "nmfx_engine_master_ptrs", "nmfx_engine_init_f64", "nmfx_last_call_exchange", "nmfx_rccl_library", "nmfx_abi_sizes",
-    "nmfx_cmfwisa", "nmfx_seminmf", "nmfx_kmeans", "nmfx_nmf_f64", "nmfx_nmf_batch", "nmfx_cnmf_batch", "nmfx_wnmf", "nmfx_wcnmf", "nmfx_wnmf_batch", "nmfx_wcnmf_batch", "nmfx_softmask", "nmfx_softmask_dev", "nmfx_impute",
+    "nmfx_cmfwisa", "nmfx_seminmf", "nmfx_kmeans", "nmfx_nmf_f64", "nmfx_nmf_batch", "nmfx_cnmf_batch", "nmfx_wnmf", "nmfx_wcnmf", "nmfx_wnmf_batch", "nmfx_wcnmf_batch", "nmfx_softmask", "nmfx_softmask_dev", "nmfx_impute", "nmfx_engine_plan",
 ]
 
 
@@ -133,6 +133,7 @@ def load():
     lib.nmfx_projfunc_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
     lib.nmfx_engine_workspace_bytes.argtypes = [C.POINTER(EngineDesc), C.POINTER(C.c_size_t)]
     lib.nmfx_engine_packed_count.argtypes = [C.POINTER(EngineDesc), C.POINTER(C.c_size_t)]
+    lib.nmfx_engine_plan.argtypes = [C.POINTER(EngineDesc), C.POINTER(C.c_int32), C.c_int32]
     lib.nmfx_engine_create.argtypes = [C.POINTER(EngineDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.nmfx_engine_is_fused.argtypes = [C.c_void_p]
     lib.nmfx_engine_defer_hstep_finish.argtypes = [C.c_void_p, C.c_int32]
@@ -174,6 +175,33 @@ def load():
 def check(status):
     if status != NMFX_OK:
         raise NmfxError(status, load().nmfx_last_error().decode("utf-8", "replace"))
+
+
+# the indices of nmfx_engine_plan's output (include/nmfx.h: NMFX_PLAN_*), in order
+PLAN_FIELDS = ("fused", "use_vt", "nsplit_w", "isplit_h", "nsplit_T", "klw_hsplit", "dual", "dual2", "h_update_in_epilogue", "hug", "fused_T", "klw")
+ALGORITHMS = {"nmf": 0, "cnmf": 1, "lnmf": 2}
+
+
+def engine_plan(desc=None, **fields):
+    """nmfx_engine_plan: which kernels an engine of this descriptor would run -> dict over PLAN_FIELDS.  Host-only, no GPU needed.  `desc` is an EngineDesc, or
+    the descriptor's fields by name (m, n_local, K_total, T = 1, divergence, alpha, beta, algorithm = a code or "nmf" / "cnmf" / "lnmf", path, flags, fixH_row, ...)"""
+    keep = []
+    if desc is None:
+        desc = EngineDesc()
+        fields = dict(dict(T=1, alpha=1.0, beta=1.0), **fields)
+        for k, v in fields.items():
+            if k == "algorithm" and isinstance(v, str):
+                v = ALGORITHMS[v]
+            if k in ("lamW_col", "lamH_row", "fixW_col", "fixH_row") and v is not None:
+                import numpy as np
+                arr = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32 if k.startswith("lam") else np.uint8), (int(fields["K_total"]),)))
+                keep.append(arr)
+                v = arr.ctypes.data_as(C.c_void_p)
+            setattr(desc, k, v)
+    out = (C.c_int32 * len(PLAN_FIELDS))()
+    check(load().nmfx_engine_plan(C.byref(desc), out, len(PLAN_FIELDS)))
+    del keep
+    return dict(zip(PLAN_FIELDS, (int(x) for x in out)))
 
 
 def device_count():

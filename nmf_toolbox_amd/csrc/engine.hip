@@ -344,6 +344,21 @@ nmfx_status fill_from_desc(nmfx_engine *e, const nmfx_engine_desc *d) {
     return NMFX_OK;
 }
 
+// The branches of the fused H step (nmfx_engine_hstep), as predicates of the filled engine: the step itself and nmfx_engine_plan both decide through them.
+// euclidean: the H update in Gram form, H .* Gn ./ (W'*W*H) with the K x K product folded into the update kernel (small_mm.hip)
+inline bool h_step_gram_update(const nmfx_engine *e) { return e->div == NMFX_DIV_EUCLIDEAN && e->algo != 3 && h_update_gram_supported(e->K); }
+// euclidean: the numerator W'*V has no first product and leaves the H-step form of the stationary kernel: 1 = the W-step form over the transposed copy of V
+// (have_vt: the copy exists), 2 = the pipelined two-operand GEMM (K % 64 != 0 would drop it to its unaligned kernel), 0 = it stays
+inline int h_step_plain_numerator(const nmfx_engine *e, bool have_vt) {
+    if (e->dual || e->div == NMFX_DIV_KL) return 0;
+    return have_vt ? 1 : (e->K % 64 == 0 ? 2 : 0);
+}
+// ... and the fused kernel updates H in its own epilogue (EPI == 1: float64 master and fp32 image, no Gn / Gp) when one workgroup owns all of a column block's
+// sum -- no split over the rows of W -- and the update is the plain multiplicative one on one numerator / denominator pair
+inline bool h_update_in_epilogue(const nmfx_engine *e, bool have_vt) {
+    return e->fused && !e->all_fixH && h_step_plain_numerator(e, have_vt) == 0 && e->isplit_h == 1 && e->algo != 3 && !h_step_gram_update(e) && !e->dual2;
+}
+
 // X*X' (K x K) for X = K x len with contiguous columns, on the W-step form of the stationary kernel: D = X plays V (K "rows"), the columns of X
 // are streamed through LDS by DMA exactly like the columns of H in the W step -- out(k, r) = sum_c X(r, c) X(k, c)
 nmfx_status gram_fused(nmfx_engine *e, const float *X, long len, float *G) {
@@ -888,6 +903,27 @@ nmfx_status nmfx_engine_packed_count(const nmfx_engine_desc *d, size_t *count) {
     *count = layout(&tmp, nullptr).packed_count;
     return NMFX_OK;
 }
+nmfx_status nmfx_engine_plan(const nmfx_engine_desc *d, int32_t *out, int32_t capacity) {
+    if (!out || capacity < NMFX_PLAN_COUNT) { set_error("nmfx_engine_plan: out needs room for NMFX_PLAN_COUNT = %d entries", (int)NMFX_PLAN_COUNT); return NMFX_ERR_INVALID; }
+    nmfx_engine tmp{};
+    TRY(fill_from_desc(&tmp, d));
+    tmp.all_fixH = d->fixH_row != nullptr;   // as nmfx_engine_create reads the descriptor's switches: every row fixed = no H step at all
+    for (int k = 0; k < tmp.K && tmp.all_fixH; ++k) tmp.all_fixH = d->fixH_row[k] != 0;
+    const bool fusedT = tmp.fusedT || tmp.fusedT_kl || tmp.fusedT_dual;
+    out[NMFX_PLAN_FUSED] = tmp.fused;
+    out[NMFX_PLAN_USE_VT] = tmp.use_vt;
+    out[NMFX_PLAN_NSPLIT_W] = tmp.nsplit_w;
+    out[NMFX_PLAN_ISPLIT_H] = tmp.isplit_h;
+    out[NMFX_PLAN_NSPLIT_T] = (fusedT || tmp.klw || tmp.eucw || tmp.dualw) ? tmp.nsplit_T : 0;
+    out[NMFX_PLAN_KLW_HSPLIT] = (tmp.klw || tmp.eucw || tmp.dualw) ? tmp.klw_hsplit : 0;
+    out[NMFX_PLAN_DUAL] = tmp.dual;
+    out[NMFX_PLAN_DUAL2] = tmp.dual2;
+    out[NMFX_PLAN_H_UPDATE_IN_EPILOGUE] = h_update_in_epilogue(&tmp, tmp.use_vt);
+    out[NMFX_PLAN_HUG] = tmp.fused && h_step_gram_update(&tmp);
+    out[NMFX_PLAN_FUSED_T] = fusedT;
+    out[NMFX_PLAN_KLW] = tmp.klw;
+    return NMFX_OK;
+}
 
 nmfx_status nmfx_engine_create(const nmfx_engine_desc *d, const float *V, float *W, float *H, void *workspace, size_t workspace_bytes,
                                float *packed, nmfx_engine **out) {
@@ -1351,7 +1387,8 @@ nmfx_status nmfx_engine_hstep(nmfx_engine *e) {
         if (e->all_fixH) return NMFX_OK;
         // euclidean: W'*V_hat = (W'*W)*H.  W'*W from the transposed copy of W (rows of W contiguous: every MFMA operand one coalesced load);
         // the product with H is folded into the H update (small_mm.hip), except for constrainednmf, whose update sums over label segments first
-        const bool hug = e->div == NMFX_DIV_EUCLIDEAN && e->algo != 3 && h_update_gram_supported(e->K);
+        const bool hug = h_step_gram_update(e);
+        const int plain = h_step_plain_numerator(e, e->VT != nullptr);
         if (e->div == NMFX_DIV_EUCLIDEAN) {
             Scope s(e, TAG_GRAM);
             TRY(gram_fused(e, e->WT, e->m, e->GW));
@@ -1370,7 +1407,7 @@ nmfx_status nmfx_engine_hstep(nmfx_engine *e) {
             f.ab_alpha = (float)e->alpha; f.ab_beta = (float)e->beta; f.inv_exp = outer_exp(e);
             if (e->Valpha) f.D = e->Valpha;
         }
-        if (func == 0 && e->VT) {
+        if (plain == 1) {
             // euclidean: the numerator W'*V has no first product.  The H-step form of the stationary kernel reads its V tile with the lanes
             // ACROSS columns (16-byte pieces at stride m) and, with half the MFMA work per tile to hide that under, ran 0.61 ms at C2; the
             // pipelined two-operand GEMM 0.60 ms (0.75 of peak).  V never changes, so a transposed copy made once turns the product into
@@ -1394,7 +1431,7 @@ nmfx_status nmfx_engine_hstep(nmfx_engine *e) {
             else if (e->algo == 3) TRY(z_update(e->st, e->Z, e->H, e->Gn, e->Gp, e->Gpvec, e->K, e->nz, e->seg_dev, e->lamH, e->fixH, 1.0f, 0));
             else TRY(h_update(e->st, e->H, e->Gn, e->Gp, nullptr, e->K, e->n, e->lamH, e->fixH, 1.0f, 1, 0, e->H64));
             }
-        } else if (func == 0 && e->K % 64 == 0) {   // K % 64 != 0 would drop the GEMM to its unaligned (general) kernel
+        } else if (plain == 2) {   // K % 64 != 0 would drop the GEMM to its unaligned (general) kernel
             // euclidean: the numerator W'*V needs no first product, so the register-stationary kernel has half the MFMA work
             // per tile barrier; the pipelined GEMM runs this plain contraction faster (C2: 0.87 -> ~0.6 ms)
             {
@@ -1411,7 +1448,7 @@ nmfx_status nmfx_engine_hstep(nmfx_engine *e) {
             if (hug) { TRY(h_update_gram(e->st, e->H, e->GW, e->Gn, 1, 0, e->K, e->n, e->lamH, e->fixH, e->H64)); }
             else if (e->algo == 3) TRY(z_update(e->st, e->Z, e->H, e->Gn, e->Gp, e->Gpvec, e->K, e->nz, e->seg_dev, e->lamH, e->fixH, 1.0f, 0));
             else TRY(h_update(e->st, e->H, e->Gn, e->Gp, nullptr, e->K, e->n, e->lamH, e->fixH, 1.0f, 1, 0, e->H64));
-        } else if (e->isplit_h == 1 && e->algo != 3 && !hug && !e->dual2) {
+        } else if (h_update_in_epilogue(e, e->VT != nullptr)) {
             f.Hio = e->H; f.H64 = e->H64; f.den = kl ? nullptr : e->Gp; f.denvec = kl ? e->Gpvec : nullptr; f.lam = e->lamH; f.fix = e->fixH;
             f.sqrt_rule = e->algo == 2;
             Scope s(e, TAG_FUSED_H);
