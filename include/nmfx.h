@@ -340,6 +340,32 @@ nmfx_status nmfx_softmask_dev(void *stream, int64_t m, int64_t n, int32_t num_so
 nmfx_status nmfx_impute(int64_t m, int64_t N, int32_t K, int32_t T, int32_t dtype, const void *V, const void *M, const void *W, const void *H,
                         int32_t batch, const int64_t *col_offsets /* batch + 1, col_offsets[0] = 0, increasing */, int32_t w_per_problem,
                         int32_t divergence, void *Y /* or NULL */, double *fit /* [batch] or NULL */, double *held /* [batch] or NULL */, int32_t device);
+/* nmfx_impute's pass on ONE problem whose operands already live on the device, asynchronous on `stream`: nothing is allocated, copied to or
+ * from the host or waited for, and nmfx_last_call_timing is left alone; the problem's geometry travels in the kernel arguments, no table is uploaded.
+ * V_dev is an m x n view of float32 with a leading dimension, in either layout -- the element strides of (i, j):
+ *   layout 0, column-major: V[i + ldv*j], ldv >= m (the pass nmfx_impute runs);   layout 1, row-major: V[i*ldv + j], ldv >= n (the MFMA operands change
+ *   places, so that every access to V, M and Y is still 32 consecutive elements)
+ * M_dev is a view of the same shape and layout with its own leading dimension ldm: float32 weights, >= 0 and finite (m_kind 0: on = M > 0), or bytes
+ * (m_kind 1: a bool / uint8 mask, on = M != 0 with weight 1).  W_dev and H_dev are the fp32 images the kernel contracts, W[i + m*(t*K + k)] and
+ * H[k + K*j], >= 0 and finite (not checked here).  There is no alignment requirement beyond the element.  Exactly one of Y_dev and scores_dev is given:
+ *   Y_dev       the fill, on ? V : S, a float32 view in V's layout with leading dimension ldy; only its m x n elements are written.  Both layouts give
+ *               the same bits, and layout 0 gives nmfx_impute's.
+ *   scores_dev  doubles: [2] = fit, held of nmfx_impute's definition for `divergence`; with frames != 0 [2*n] = fit[0..n), held[0..n), the two sums over
+ *               the rows of one column each.  Two launches: the pass writes float64 partials into work_dev (work_bytes at least what
+ *               nmfx_impute_dev_work_bytes(m, n, frames) answers: 16 bytes per 128 x 64 tile, or per (row tile of 128, column)), a finishing kernel
+ *               reduces them in an order that depends on (m, n) only -- not on the grid, NMFX_IMPUTE_MAX_GRID or the stream.  No atomics: two calls return
+ *               the same bits.  The totals need not be the bits of nmfx_impute's, whose sum over the tiles is serial.
+ * NMFX_ERR_INVALID, before any device call: a NULL V_dev, M_dev, W_dev or H_dev; Y_dev and scores_dev both NULL or both given; a size <= 0; ldv, ldm (or
+ * ldy with Y_dev) below the contiguous extent; another layout, m_kind or frames; scores with a divergence that is none of the three; frames with Y_dev;
+ * scoring with work_dev NULL or work_bytes below the query's answer.  NMFX_ERR_UNSUPPORTED: T > 64, NMFX_DIV_AB.  NMFX_IMPUTE_MAX_GRID is read per call,
+ * as by nmfx_impute.  New entry points; no structure grows, so NMFX_VERSION stays 600. */
+nmfx_status nmfx_impute_dev_work_bytes(int64_t m, int64_t n, int32_t frames, size_t *bytes);
+nmfx_status nmfx_impute_dev(void *stream, int64_t m, int64_t n, int32_t K, int32_t T, int32_t layout /* 0 column-major, 1 row-major */,
+                            const float *V_dev, int64_t ldv, const void *M_dev, int64_t ldm, int32_t m_kind /* 0 float32 weights, 1 bytes (non-zero = 1) */,
+                            const float *W_dev, const float *H_dev, int32_t divergence,
+                            float *Y_dev, int64_t ldy,                 /* fill, or NULL */
+                            double *scores_dev,                        /* score: [2] = fit, held; with frames [2*n] = fit[0..n), held[0..n); or NULL */
+                            int32_t frames, void *work_dev, size_t work_bytes, int32_t device);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,

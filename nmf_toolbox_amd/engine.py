@@ -8,6 +8,8 @@ torch tensor of shape (n, m).
 Multi-GPU: V and H are column-sharded, W is replicated; per iteration ONE all-reduce
 of the packed W-step partials [N | P] (KL: [N | rowsum(H)]).  Everything after the all-reduce is
 computed redundantly and identically on every rank, so W stays bit-identical across ranks.
+
+Single fused passes on torch tensors, at the end of this file: softmask (nmfx_softmask_dev), impute and holdout (nmfx_impute_dev).
 """
 from __future__ import annotations
 
@@ -503,6 +505,80 @@ def _softmask_images(W32, H32, dev):
     return Wimg, Himg
 
 
+def _real_entry(fn):
+    """entry(a, name) for an entry of W or H of the device calls: a torch tensor stays where it is, anything else goes the way the host calls take it"""
+    import torch
+
+    def real(a, name):
+        if isinstance(a, torch.Tensor):
+            if a.is_complex() or not (a.is_floating_point() or a.dtype in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
+                raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
+            return a.detach() if a.is_floating_point() else a.detach().to(torch.float64)
+        a = np.asarray(a)
+        if a.dtype.kind not in "buif":
+            raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
+        return a if a.dtype.kind == "f" else a.astype(np.float64)
+    return real
+
+
+def _factors32(fn, Wl, Hl, check, flags):
+    """The values of W and H on the fp32 images the device contracts -> ([W_i], [H_i]) as float32 torch tensors.  numpy entries are checked on the host as
+    the host calls check them; torch entries where they live: with `check`, a flag pair (not finite, negative) per entry is appended to flags[device], to
+    be read back together by _raise_flags (the one synchronisation nmfx_check = False avoids)."""
+    import torch
+    W32, H32 = [], []
+    for name, src, dst in (("W", Wl, W32), ("H", Hl, H32)):
+        for a in src:
+            if isinstance(a, torch.Tensor):
+                a32 = a.to(torch.float32)
+                if check and a32.numel():
+                    flags.setdefault(a32.device, []).append((name, torch.stack([~torch.isfinite(a32).all(), (a32 < 0).any()])))
+            else:
+                with np.errstate(over="ignore"):
+                    a32 = a.astype(np.float32, copy=False)
+                if not np.all(np.isfinite(a32)):
+                    raise ValueError("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name))
+                if a.size and a.min() < 0:
+                    raise ValueError("%s: every entry of %s must be >= 0" % (fn, name))
+                a32 = torch.from_numpy(np.ascontiguousarray(a32) if a32.flags.writeable else a32.copy())   # (torch takes no read-only array)
+            dst.append(a32)
+    return W32, H32
+
+
+def _raise_flags(flags, messages):
+    """read the flag pairs back, one transfer per device, and raise for the first that is set: messages[name] = (when not finite, when negative)"""
+    import torch
+    for dev, fl in flags.items():
+        bad = torch.stack([f for _, f in fl]).cpu().numpy()
+        for (name, _), (notfinite, negative) in zip(fl, bad):
+            if notfinite:
+                raise ValueError(messages[name][0])
+            if negative:
+                raise ValueError(messages[name][1])
+
+
+def _factor_messages(fn):
+    return {name: ("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name), "%s: every entry of %s must be >= 0" % (fn, name))
+            for name in ("W", "H")}
+
+
+def _view_layouts(t):
+    """the layouts a 2-D tensor's strides fit, as {layout: leading dimension}: 1 row-major (ld, 1) with ld >= n, 0 column-major (1, ld) with ld >= m; the
+    first key is the one the strides say (a single row or column fits both: it is column-major only where its strides say (1, ld))"""
+    m, n = int(t.shape[0]), int(t.shape[1])
+    s0, s1 = int(t.stride(0)), int(t.stride(1))
+    row_ok = (n == 1 or s1 == 1) and (m == 1 or s0 >= n)
+    col_ok = (m == 1 or s0 == 1) and (n == 1 or s1 >= m)
+    out = {}
+    if row_ok and not (col_ok and s0 == 1 and s1 != 1):
+        out[1] = s0 if m > 1 else n
+    if col_ok:
+        out[0] = s1 if n > 1 else m
+    if row_ok and 1 not in out:
+        out[1] = s0 if m > 1 else n
+    return out
+
+
 def softmask(X, W, H, config=None):
     """Y = engine.softmask(X, W, H, config): toolbox.softmask on a mixture that lives on the GPU, launched on torch's current stream of X's device; the
     estimates (or masks) stay there.  Same definition, same kernel arithmetic and the same config keys ('power', 'output', 'sources').
@@ -533,52 +609,20 @@ def softmask(X, W, H, config=None):
         raise ValueError("%s: X must be real or complex; got %s" % (fn, X.dtype))
     m, n = int(X.shape[0]), int(X.shape[1])
 
-    def real(a, name):      # an entry of W or H: a torch tensor stays where it is, anything else goes the way softmask takes it
-        if isinstance(a, torch.Tensor):
-            if a.is_complex() or not (a.is_floating_point() or a.dtype in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
-                raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
-            return a.detach() if a.is_floating_point() else a.detach().to(torch.float64)
-        a = np.asarray(a)
-        if a.dtype.kind not in "buif":
-            raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
-        return a if a.dtype.kind == "f" else a.astype(np.float64)
-    Wl, Hl = TB._softmask_factors(fn, W, H, cfg, real=real)
+    Wl, Hl = TB._softmask_factors(fn, W, H, cfg, real=_real_entry(fn))
     Ks, T = TB._softmask_shapes(fn, m, n, Wl, Hl)
     # the values, on the fp32 images the device contracts: numpy entries on the host as softmask checks them, torch entries where they live (one flag pair
     # per device, read back together: the one synchronisation nmfx_check = False avoids)
-    W32, H32, flags = [], [], {}
-    for name, src, dst in (("W", Wl, W32), ("H", Hl, H32)):
-        for a in src:
-            if isinstance(a, torch.Tensor):
-                a32 = a.to(torch.float32)
-                if check and a32.numel():
-                    flags.setdefault(a32.device, []).append((name, torch.stack([~torch.isfinite(a32).all(), (a32 < 0).any()])))
-            else:
-                with np.errstate(over="ignore"):
-                    a32 = a.astype(np.float32, copy=False)
-                if not np.all(np.isfinite(a32)):
-                    raise ValueError("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name))
-                if a.size and a.min() < 0:
-                    raise ValueError("%s: every entry of %s must be >= 0" % (fn, name))
-                a32 = torch.from_numpy(np.ascontiguousarray(a32) if a32.flags.writeable else a32.copy())   # (torch takes no read-only array)
-            dst.append(a32)
-    for dev, fl in flags.items():
-        bad = torch.stack([f for _, f in fl]).cpu().numpy()
-        for (name, _), (notfinite, negative) in zip(fl, bad):
-            if notfinite:
-                raise ValueError("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name))
-            if negative:
-                raise ValueError("%s: every entry of %s must be >= 0" % (fn, name))
+    flags = {}
+    W32, H32 = _factors32(fn, Wl, Hl, check, flags)
+    _raise_flags(flags, _factor_messages(fn))
     if X.dtype not in (torch.float32, torch.complex64):
         raise ValueError("%s: X must be float32 or complex64 on the device; got %s.  The host call softmask serves float64 / complex128 (and every other "
                          "dtype, as float64); nothing runs silently in another precision" % (fn, X.dtype))
     s0, s1 = int(X.stride(0)), int(X.stride(1))
-    row_ok = (n == 1 or s1 == 1) and (m == 1 or s0 >= n)
-    col_ok = (m == 1 or s0 == 1) and (n == 1 or s1 >= m)
-    if row_ok and not (col_ok and s0 == 1 and s1 != 1):      # (a single row or column fits both: it is column-major only where its strides say (1, ld))
-        layout, ld = 1, (s0 if m > 1 else n)
-    elif col_ok:
-        layout, ld = 0, (s1 if n > 1 else m)
+    fits = _view_layouts(X)
+    if fits:
+        layout, ld = next(iter(fits.items()))
     else:
         raise ValueError("%s: X must have one unit stride and the other at least the extent, without overlap (row-major (ld, 1) with ld >= n, or column-major "
                          "(1, ld) with ld >= m); got shape %r with strides %r -- pass X.contiguous()" % (fn, (m, n), (s0, s1)))
@@ -604,3 +648,128 @@ def softmask(X, W, H, config=None):
                                      C.c_void_p(Wimg.data_ptr()), C.c_void_p(Himg.data_ptr()), float(power), int(masks), C.c_void_p(out.data_ptr()), ldy,
                                      m * n, dev.index if dev.index is not None else torch.cuda.current_device()))
     return Y
+
+
+def _impute_dev(fn, V, M, W, H, config, scores):
+    """engine.impute (scores False) and engine.holdout (scores True): the checks, the two fp32 images, the one call into nmfx_impute_dev"""
+    import torch
+    from . import toolbox as TB
+    host = fn.split(".")[-1]
+    cfg = config if config else {}
+    div = TB._impute_config(fn, cfg, scores)
+    check = cfg.get("nmfx_check", True)
+    if not isinstance(check, (bool, np.bool_)):
+        raise ValueError("%s: nmfx_check must be True or False; got %r" % (fn, check))
+    frames = False
+    if "frames" in cfg:
+        if not scores:
+            raise ValueError("%s: frames is a key of engine.holdout (one pair of scores per column); a fill has none" % fn)
+        frames = cfg["frames"]
+        if not isinstance(frames, (bool, np.bool_)):
+            raise ValueError("%s: frames must be True or False; got %r" % (fn, frames))
+        frames = bool(frames)
+    for name, a in (("V", V), ("M", M)):
+        if not isinstance(a, torch.Tensor):
+            raise ValueError("%s: %s must be a torch tensor (the host call %s takes arrays); got %s" % (fn, name, host, type(a).__name__))
+    if V.dim() != 2:
+        raise ValueError("%s: V must be a matrix" % fn)
+    real_kinds = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+    if V.is_complex() or not (V.is_floating_point() or V.dtype in real_kinds):
+        raise ValueError("%s: V must be real (bool, integer or float); got %s" % (fn, V.dtype))
+    m, n = int(V.shape[0]), int(V.shape[1])
+    if m < 1 or n < 1:
+        raise ValueError("%s: V must not be empty; got %d x %d" % (fn, m, n))
+    if tuple(M.shape) != (m, n):
+        raise ValueError("%s: M must have the shape of V, %r; got %r" % (fn, (m, n), tuple(M.shape)))
+    if M.is_complex() or not (M.is_floating_point() or M.dtype in real_kinds):
+        raise ValueError("%s: M must be bool, integer or float; got %s" % (fn, M.dtype))
+    Wl, Hl, T = TB._impute_factor_shapes(fn, W, H, m, n, entry=_real_entry(fn))
+    flags = {}
+    W32, H32 = _factors32(fn, Wl, Hl, check, flags)
+    if V.dtype != torch.float32:
+        raise ValueError("%s: V must be float32 on the device; got %s.  The host call %s serves float64 (and every other dtype, as float64); nothing runs "
+                         "silently in another precision" % (fn, V.dtype, host))
+    if M.dtype not in (torch.float32, torch.bool, torch.uint8):
+        raise ValueError("%s: M must be float32 (weights) or torch.bool / torch.uint8 (a mask: non-zero = observed, weight 1) on the device; got %s -- "
+                         "convert it first (M.float(), or M > 0)" % (fn, M.dtype))
+    fits = _view_layouts(V)
+    for name, a in (("V", V), ("M", M)):
+        if not _view_layouts(a):
+            raise ValueError("%s: %s must have one unit stride and the other at least the extent, without overlap (row-major (ld, 1) with ld >= n, or "
+                             "column-major (1, ld) with ld >= m); got shape %r with strides %r -- pass %s.contiguous()" % (fn, name, (m, n), tuple(a.stride()), name))
+    layout, ldv = next(iter(fits.items()))
+    if M.device != V.device:
+        raise ValueError("%s: M must live on V's device, %s; got %s" % (fn, V.device, M.device))
+    if layout not in _view_layouts(M):
+        raise ValueError("%s: M must be in V's layout class (%s); got strides %r beside V's %r" % (fn, "row-major" if layout else "column-major",
+                                                                                                   tuple(M.stride()), tuple(V.stride())))
+    ldm = _view_layouts(M)[layout]
+    for name, a in (("V", V), ("M", M)):
+        if a.is_conj() or a.is_neg():
+            raise ValueError("%s: %s is a lazy conjugate or negative view: call .resolve_conj() (.resolve_neg()) on it first" % (fn, name))
+    # the values, where they live: W and H (above), a float32 M, and for the scores V; all flags of a device are read back together
+    messages = _factor_messages(fn)
+    messages["M"] = ("%s: every weight in M must be finite" % fn, "%s: every weight in M must be >= 0" % fn)
+    messages["V"] = ("%s: every entry of V must be finite: the hidden entries must be known to be scored (V is read where M == 0 too)" % fn, "")
+    if check:
+        if M.dtype == torch.float32:
+            flags.setdefault(M.device, []).append(("M", torch.stack([~torch.isfinite(M).all(), (M < 0).any()])))
+        if scores:
+            flags.setdefault(V.device, []).append(("V", torch.stack([~torch.isfinite(V).all(), torch.zeros((), dtype=torch.bool, device=V.device)])))
+    _raise_flags(flags, messages)
+    if not V.is_cuda:
+        raise _lib.NmfxError(_lib.NMFX_ERR_NO_DEVICE, "%s needs a CUDA/HIP tensor V: there is no CPU fallback" % fn)
+    dev = V.device
+    K = int(sum(w.shape[1] for w in W32))
+    Wimg, Himg = _softmask_images(W32, H32, dev)
+    lib = _lib.load()
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    m_kind = 0 if M.dtype == torch.float32 else 1
+    common = (stream, m, n, K, T, layout, C.c_void_p(V.data_ptr()), ldv, C.c_void_p(M.data_ptr()), ldm, m_kind, C.c_void_p(Wimg.data_ptr()),
+              C.c_void_p(Himg.data_ptr()))
+    if not scores:
+        if layout == 1:
+            Y, ldy = torch.empty((m, n), dtype=torch.float32, device=dev), n
+            ptr = Y.data_ptr()
+        else:
+            out = torch.empty((n, m), dtype=torch.float32, device=dev)
+            Y, ldy, ptr = out.t(), m, out.data_ptr()
+        _lib.check(lib.nmfx_impute_dev(*common, -1, C.c_void_p(ptr), ldy, None, 0, None, 0, index))
+        return Y
+    need = C.c_size_t()
+    _lib.check(lib.nmfx_impute_dev_work_bytes(m, n, int(frames), C.byref(need)))
+    work = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(2 * n if frames else 2, dtype=torch.float64, device=dev)
+    _lib.check(lib.nmfx_impute_dev(*common, int(div), None, 0, C.c_void_p(out.data_ptr()), int(frames), C.c_void_p(work.data_ptr()), need.value, index))
+    return (out[:n], out[n:]) if frames else (out[0], out[1])
+
+
+def impute(V, M, W, H, config=None):
+    """Y = engine.impute(V, M, W, H, config): toolbox.impute on data that lives on the GPU, launched on torch's current stream of V's device; the result
+    stays there.  Same definition (Y = M > 0 ? V : S with S = sum_i sum_t W_i(:,:,t) * rshift_t(H_i) in fp32) and the same kernel arithmetic.
+
+    V: a 2-D float32 torch tensor, m x n, with one unit stride and the other at least the extent: row-major (stride (ld, 1), ld >= n) or column-major
+    (stride (1, ld), ld >= m); slices of wider / taller tensors are fine and a view may begin at any element.  V is passed by pointer, never copied; the
+    kernel has a form for either layout and both give the same bits (the column-major ones are toolbox.impute's).
+    M: a tensor of V's shape on V's device in V's layout class, with its own leading dimension: float32 weights (>= 0 and finite), or torch.bool /
+    torch.uint8 (observed where non-zero, weight 1: `torch.rand_like(V) > 0.3` as it is, one byte of traffic per element instead of four).
+    W, H: single arrays or lists per source (summed), in natural shape (m x K_i x T or m x K_i, and K_i x n); every entry a numpy array or a torch tensor
+    on any device with any strides.  Their two fp32 images are built on V's device with torch ops.
+    config['nmfx_check'] (default True): check where they live that torch entries of W and H and a float32 M are finite and >= 0 (and for engine.holdout
+    that V is finite), which costs one host synchronisation; False skips the checks and the wait (numpy entries are always checked on the host).
+
+    Returns one new contiguous tensor in V's layout class: row-major in gives row-major out, column-major in a .t() view of a contiguous (n, m) tensor.
+    Refused: what toolbox.impute refuses; float64 and every other dtype of V (toolbox.impute serves them from the host); a V or M that is not 2-D,
+    without a unit stride or overlapping; M of another shape, device or layout class; lazy conj / neg views; config['frames'] (engine.holdout's)."""
+    return _impute_dev("engine.impute", V, M, W, H, config, False)
+
+
+def holdout(V, M, W, H, config=None):
+    """fit, held = engine.holdout(V, M, W, H, config): toolbox.holdout on data that lives on the GPU, launched on torch's current stream of V's device.
+    fit = sum over M > 0 of M .* d(V, S), held = sum over M == 0 of d(V, S) for config['divergence'] ('euclidean', 'kl', 'is'); the cost terms are float64
+    on (double)V and (double)S.  Two 0-dim float64 tensors on V's device: the caller decides when to .item().  With config['frames'] = True, two float64
+    tensors of length n: the two sums over the rows of one column each (a score per frame).  Two launches, no atomics: two calls return the same bits, and
+    the scores do not depend on the grid or the stream (the totals need not be the bits of toolbox.holdout, whose sum over the tiles is serial).
+    Inputs, config['nmfx_check'] and refusals as for engine.impute; V must be finite everywhere (checked with nmfx_check)."""
+    return _impute_dev("engine.holdout", V, M, W, H, config, True)

@@ -1298,10 +1298,9 @@ def _impute_config(fn, cfg, scores):
     return _DIV_WNMF[div] if scores else None
 
 
-def _impute_factors(fn, W, H, m, n, dtype, shared=None):
-    """W and H of one problem, as arrays or as lists per source (summed), against an m x n V -> W (m x K x T) and H (K x n) in `dtype`, column-major, the
-    sources side by side along K, every entry >= 0 and finite also once rounded to float32.  `shared`, a dict, keeps the travelling form of a W that
-    comes again (the batch calls' ONE W: converted and checked once, not once per problem)."""
+def _impute_factor_shapes(fn, W, H, m, n, entry=None):
+    """The structure and shape checks of W and H of one problem, as arrays or as lists per source, against an m x n V -> ([W_i as m x K_i x T], [H_i], T).
+    `entry(a, name)` makes an array of an entry and checks its kind (engine.impute / engine.holdout pass one that also lets torch tensors through)."""
     if _is_cell(W) != _is_cell(H):
         raise ValueError("%s: W and H must both be lists (one entry per source) or both be arrays" % fn)
     Wl, Hl = (list(W), list(H)) if _is_cell(W) else ([W], [H])
@@ -1309,16 +1308,21 @@ def _impute_factors(fn, W, H, m, n, dtype, shared=None):
         raise ValueError("%s: W lists %d sources, H lists %d" % (fn, len(Wl), len(Hl)))
     if len(Wl) == 0:
         raise ValueError("%s: W and H list no source" % fn)
+
+    def entry_numpy(a, name):
+        a = np.asarray(a)
+        if a.dtype.kind not in "buif":
+            raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
+        return a
+    entry = entry or entry_numpy
     Wr, Hr, T = [], [], None
     for i, (w, h) in enumerate(zip(Wl, Hl)):
-        w, h = np.asarray(w), np.asarray(h)
-        for name, a in (("W", w), ("H", h)):
-            if a.dtype.kind not in "buif":
-                raise ValueError("%s: %s must be real (bool, integer or float); got %s" % (fn, name, a.dtype))
+        w, h = entry(w, "W"), entry(h, "H")
+        wshape = tuple(w.shape)
         if w.ndim == 2:
             w = w.reshape(w.shape[0], w.shape[1], 1)
         if w.ndim != 3 or h.ndim != 2:
-            raise ValueError("%s: W of source %d must be m x K_i or m x K_i x T and H must be K_i x n; got shapes %r and %r" % (fn, i, np.shape(Wl[i]), h.shape))
+            raise ValueError("%s: W of source %d must be m x K_i or m x K_i x T and H must be K_i x n; got shapes %r and %r" % (fn, i, wshape, tuple(h.shape)))
         if w.shape[0] != m or h.shape[1] != n:
             raise ValueError("%s: V is %d x %d, source %d has W with %d rows and H with %d columns" % (fn, m, n, i, w.shape[0], h.shape[1]))
         if w.shape[1] != h.shape[0] or w.shape[1] < 1:
@@ -1330,6 +1334,14 @@ def _impute_factors(fn, W, H, m, n, dtype, shared=None):
         Hr.append(h)
     if T < 1 or T > IMPUTE_MAX_CONTEXT:
         raise ValueError("%s: the context length T = %d is not supported (1 to %d)" % (fn, T, IMPUTE_MAX_CONTEXT))
+    return Wr, Hr, int(T)
+
+
+def _impute_factors(fn, W, H, m, n, dtype, shared=None):
+    """W and H of one problem, as arrays or as lists per source (summed), against an m x n V -> W (m x K x T) and H (K x n) in `dtype`, column-major, the
+    sources side by side along K, every entry >= 0 and finite also once rounded to float32.  `shared`, a dict, keeps the travelling form of a W that
+    comes again (the batch calls' ONE W: converted and checked once, not once per problem)."""
+    Wr, Hr, T = _impute_factor_shapes(fn, W, H, m, n)
     key = (id(W), np.dtype(dtype).str)
     Wc = shared.get(key) if shared is not None else None
     with np.errstate(over="ignore"):     # (a float64 entry beyond float32's range is Inf in the fp32 image the device contracts, and refused)

@@ -142,8 +142,8 @@ def main():
     if a.stats:
         m, n, K, T = TRACE_SHAPE
         for r in from_stats(a.stats)[:12]:
-            fill = re.search(r"impute_kernel<float, 0, true, false>", r["name"])
-            score = re.search(r"impute_kernel<float, [123], false, true>", r["name"])
+            fill = re.search(r"impute_kernel<float, float, 0, true, false, 0, false, .*ImpArgs>", r["name"])   # (the kernel of csrc/impute_pass.h as nmfx_impute instantiates it)
+            score = re.search(r"impute_kernel<float, float, [123], false, true, 0, false, .*ImpArgs>", r["name"])
             store = re.search(r"wcmap_kernel<1, true, false>", r["name"])
             cost = re.search(r"wcmap_kernel<1, (true|false), true>", r["name"])
             if fill or score or store or cost:
