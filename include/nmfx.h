@@ -366,6 +366,40 @@ nmfx_status nmfx_impute_dev(void *stream, int64_t m, int64_t n, int32_t K, int32
                             float *Y_dev, int64_t ldy,                 /* fill, or NULL */
                             double *scores_dev,                        /* score: [2] = fit, held; with frames [2*n] = fit[0..n), held[0..n); or NULL */
                             int32_t frames, void *work_dev, size_t work_bytes, int32_t device);
+/* nmfx_wnmf on operands that already live on the device, on `stream`, out of one work buffer of the caller's: the same update equations,
+ * arithmetic and schedule (the cost of iteration t is a by-product of the first map pass of iteration t + 1, one cost-only pass closes the call, the stop
+ * read happens before the W update).  V_dev is an m x n view of float32 with a leading dimension, in either layout -- the element strides of (i, j):
+ *   layout 0, column-major: V[i + ldv*j], ldv >= m (the map pass nmfx_wnmf runs);   layout 1, row-major: V[i*ldv + j], ldv >= n (the MFMA operands of the
+ *   map pass change places, so that every access to V, M and the mapped operands is still 32 consecutive elements)
+ * M_dev is a view of the same shape and layout with its own leading dimension ldm: float32 weights, >= 0 and finite (m_kind 0: on = M > 0), or bytes
+ * (m_kind 1: a bool / uint8 mask, on = M != 0 with weight 1).  Both are read in place and NEVER written: V is not zeroed where M == 0 and is never looked
+ * at there.  There is no alignment requirement beyond the element.  lamW, lamH (float) and fixW, fixH (bytes, non-zero = fixed) are HOST vectors of K_total
+ * per-component values (NULL = all zero); they travel in kernel arguments and are not read after the call returns.  W_init_dev (W[i + m*k]) and H_init_dev
+ * (H[k + K_total*j]) are float64 on the device, >= 0 and finite (not checked here); the fp32 images the passes contract are their roundings.
+ * Results, all on the device: W_out_dev (m x K_total float32) and H_out_dev (K_total x n) are the fp32 images of the float64 masters, contiguous in the
+ * call's layout (layout 0: W[i + m*k], H[k + K_total*j]; layout 1: W[i*K_total + k], H[k*n + j]); cost_out_dev receives *iters_run doubles (room for
+ * maxiter); *iters_run (host) is known when the call returns.  tolerance < 0 turns the stop rule off: the call then waits for nothing, and it never
+ * allocates or frees; with the rule on the host reads 8 bytes per iteration on `stream`.
+ * nmfx_wnmf_dev_work_bytes (host-only, no device needed) answers the size of work_dev.  With al(b) = b rounded up to a multiple of 256,
+ * kt = ceil(Kc/32), g(M, N, Kc) = max(min(4*M*N*min(max(floor(kt/4), 1), 256), 4*M*N + 2^25), 4*min(M*N, 65536)*min(kt, 64)) (a bound of the split-K
+ * scratch of the library's GEMM that never falls when a size grows), tiles = min(ceil(m/128)*ceil(n/64), 8192):
+ *   bytes = c*al(4*m*n)                                  mapped operands: c = 1 for kl with float32 weights (B is M itself, read in place), else 2
+ *         + al(8*m*K) + al(8*K*n)                        float64 masters
+ *         + 3*al(4*m*K) + 3*al(4*K*n)                    fp32 images, and the two step products of each factor
+ *         + al(max(g(m, K, n), g(K, n, m)))              GEMM scratch
+ *         + al(8*tiles) + al(24*K) + al(8*K) + al(2*K)   cost partials; column statistics; lambdas; fixed flags
+ *         + al(8*maxiter) + al(2048*K)                   the cost vector; row-reduction scratch
+ * against 4*m*n*(3 kl | 4 euclidean, is) of nmfx_wnmf: V and M are not held a second time.
+ * NMFX_ERR_INVALID, before any device call: a NULL pointer (the four vectors excepted), a size or maxiter <= 0, ldv or ldm below the contiguous extent,
+ * another layout or m_kind, a divergence that is none of the three, work_bytes below the query's answer.  NMFX_ERR_UNSUPPORTED: NMFX_DIV_AB.  New entry
+ * points; no structure grows, so NMFX_VERSION stays 600. */
+nmfx_status nmfx_wnmf_dev_work_bytes(int64_t m, int64_t n, int32_t K_total, int32_t divergence, int32_t m_kind, int32_t maxiter, size_t *bytes);
+nmfx_status nmfx_wnmf_dev(void *stream, int64_t m, int64_t n, int32_t K_total, int32_t divergence, int32_t layout /* 0 column-major, 1 row-major */,
+                          const float *V_dev, int64_t ldv, const void *M_dev, int64_t ldm, int32_t m_kind /* 0 float32 weights, 1 bytes (non-zero = 1) */,
+                          const float *lamW, const float *lamH, const uint8_t *fixW, const uint8_t *fixH,   /* host, [K_total] each, or NULL */
+                          const double *W_init_dev, const double *H_init_dev, int32_t maxiter, double tolerance /* < 0: no stop rule */,
+                          void *work_dev, size_t work_bytes, float *W_out_dev, float *H_out_dev, double *cost_out_dev /* [maxiter] */,
+                          int32_t *iters_run /* host */, int32_t device);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,

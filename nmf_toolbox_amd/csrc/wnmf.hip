@@ -14,7 +14,7 @@
 // the mapped operands A and B as fp32 m x n.  The constant ones are formed once per call (M.*V for euclidean; for kl B is M itself), so the call holds
 // 4*m*n*(3 kl | 4 euclidean, is) bytes plus O((m + n)*K).
 //
-// The weighted map pass (wmap_kernel): one workgroup owns a 128 x 64 tile of S, accumulated on v_mfma_f32_32x32x2_f32 over any K >= 1 (both factors staged
+// The weighted map pass (wmap_kernel, wnmf_pass.h; here its column-major form on float weights): one workgroup owns a 128 x 64 tile of S, accumulated on v_mfma_f32_32x32x2_f32 over any K >= 1 (both factors staged
 // through LDS 16 k at a time, two buffers, the next stage in flight in registers; the K tail is zero-filled in LDS, nothing is padded in HBM).  Each of the
 // four waves holds 32 rows x 64 columns = two accumulator blocks.  The MFMA is fed transposed (first operand H', second W): the 32 lanes of a result register
 // then run along i, the contiguous dimension of V, M, A and B, so every epilogue access is a 128-byte line per half wave.  The lane's values of V and M are
@@ -34,147 +34,10 @@
 #include "api_common.h"
 #include "dev_reduce.h"
 #include "gemm_common.h"
+#include "wnmf_pass.h"
 
 namespace nmfx {
 namespace {
-
-enum WMap { WM_EUC = 0, WM_KL = 1, WM_IS = 2 };
-
-constexpr int WBM = 128, WBN = 64, WBK = 16, WLDH = WBK + 1;
-constexpr int WMAP_MAX_GRID = 8192;
-
-struct WMapArgs {
-    const float *W, *H;     // fp32 images: W[i + m*k], H[k + K*j]
-    const float *V, *M;     // m x n
-    float *A, *B;           // m x n outputs of a storing pass (either may be NULL: not needed by the divergence)
-    long m, n;
-    int K;
-    double *partials;       // [gridDim.x] weighted data-fit partials of a cost pass
-};
-
-template <int MAP, bool STORE, bool COST>
-__global__ __launch_bounds__(256, 2) void wmap_kernel(const WMapArgs g) {
-    constexpr bool NEED_V = COST || MAP != WM_EUC;   // the storing euclidean pass forms B = M.*S only
-    __shared__ float Ws[2][WBK * WBM];
-    __shared__ float Hs[2][WBN * WLDH];
-    __shared__ double sh[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-    const long tilesM = (g.m + WBM - 1) / WBM, tilesN = (g.n + WBN - 1) / WBN, tiles = tilesM * tilesN;
-    const int K = g.K, nk = (K + WBK - 1) / WBK;
-    // loaders: consecutive threads along the operand's contiguous dimension (W: i, H: k)
-    const int w_r = tid & (WBM - 1), w_k = tid >> 7;      // + 2 u, u < 8
-    const int h_k = tid & (WBK - 1), h_c = tid >> 4;      // + 16 u, u < 4
-    double part = 0.0;
-    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
-        const long i0 = (t % tilesM) * WBM, j0 = (t / tilesM) * WBN;
-        float rw[8], rh[4];
-        auto gload = [&](int k0) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const long i = i0 + w_r;
-                const int k = k0 + w_k + 2 * u;
-                rw[u] = (i < g.m && k < K) ? g.W[i + g.m * k] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const long j = j0 + h_c + 16 * u;
-                const int k = k0 + h_k;
-                rh[u] = (j < g.n && k < K) ? g.H[k + (long)K * j] : 0.0f;
-            }
-        };
-        auto lstore = [&](int buf) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) Ws[buf][(w_k + 2 * u) * WBM + w_r] = rw[u];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) Hs[buf][(h_c + 16 * u) * WLDH + h_k] = rh[u];
-        };
-        f32x16 acc[2];
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[y][e] = 0.0f;
-        gload(0);
-        lstore(0);
-        // this lane's elements of M (and V), requested behind the first stage: they arrive under the contraction.
-        // acc[y][e]: column (lane & 31) -> i, row (e & 3) + 8 (e >> 2) + 4 (lane >> 5) -> j
-        // (An element outside the matrix reads the clamped address of one inside instead of a guarded load: 32 live predicates are 64 scalar registers.  The
-        // epilogue skips those elements.)
-        const long i = i0 + 32 * wv + l31, ic = i < g.m ? i : g.m - 1;
-        f32x16 vreg[2], mreg[2];
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const long j = j0 + 32 * y + (e & 3) + 8 * (e >> 2) + 4 * lh, jc = j < g.n ? j : g.n - 1;
-                mreg[y][e] = g.M[ic + g.m * jc];
-                vreg[y][e] = NEED_V ? g.V[ic + g.m * jc] : 0.0f;
-            }
-        __builtin_amdgcn_sched_barrier(0);   // (or the compiler sinks every one of them to its first use)
-        __syncthreads();
-        for (int kt = 0; kt < nk; ++kt) {
-            const int buf = kt & 1;
-            if (kt + 1 < nk) gload((kt + 1) * WBK);
-            const float *a = Ws[buf], *b = Hs[buf];
-#pragma unroll
-            for (int kk = 0; kk < WBK / 2; ++kk) {
-                const int k = 2 * kk + lh;
-                const float wf = a[k * WBM + 32 * wv + l31];
-#pragma unroll
-                for (int y = 0; y < 2; ++y) {
-                    const float hf = b[(32 * y + l31) * WLDH + k];
-                    acc[y] = __builtin_amdgcn_mfma_f32_32x32x2f32(hf, wf, acc[y], 0, 0, 0);   // D(row = j, col = i)
-                }
-            }
-            if (kt + 1 < nk) lstore(buf ^ 1);   // (the other buffer: last read one trip ago, behind the barrier below)
-            __syncthreads();
-        }
-        // The element map, the float64 logarithm of a cost pass most of all, is long: unrolled over the 32 results of a lane the kernel runs out of registers.
-        // The loop over the two accumulator blocks stays rolled; a rolled loop cannot index registers, so the second block moves into the first one's place.
-#pragma unroll 1
-        for (int y = 0; y < 2; ++y) {
-            const f32x16 s16 = acc[0], v16 = vreg[0], m16 = mreg[0];
-            acc[0] = acc[1]; vreg[0] = vreg[1]; mreg[0] = mreg[1];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const long j = j0 + 32 * y + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                const float s = s16[e], v = v16[e], w = m16[e];
-                const bool on = w > 0.0f && i < g.m && j < g.n;
-                const long idx = i + g.m * j;
-                if constexpr (STORE) {
-                    if (i < g.m && j < g.n) {
-                        if constexpr (MAP == WM_EUC) g.B[idx] = on ? w * s : 0.0f;
-                        else if constexpr (MAP == WM_KL) g.A[idx] = on ? (w * v) / s : 0.0f;            // nmf.m:152
-                        else { g.A[idx] = on ? (w * v) / (s * s) : 0.0f; g.B[idx] = on ? w / s : 0.0f; }   // nmf.m:155-156
-                    }
-                }
-                if constexpr (COST) {
-                    const double sd = (double)s, vd = (double)v;
-                    double c;
-                    if constexpr (MAP == WM_EUC) { const double d = vd - sd; c = d * d; }              // nmf.m:208 (0.5 applied to the sum)
-                    else if constexpr (MAP == WM_KL) c = (vd * log(vd / sd) - vd) + sd;                 // nmf.m:210
-                    else c = (log(sd / vd) + vd / sd) - 1.0;                                            // nmf.m:212
-                    part += on ? (double)w * c : 0.0;
-                }
-            }
-        }
-    }
-    if constexpr (COST) {
-        part = block_sum256(part, sh);
-        if (tid == 0) g.partials[blockIdx.x] = part;
-    }
-}
-
-long wmap_grid(long m, long n) { return std::min<long>(((m + WBM - 1) / WBM) * ((n + WBN - 1) / WBN), WMAP_MAX_GRID); }
-
-template <int MAP>
-nmfx_status wmap_launch(hipStream_t st, const WMapArgs &g, bool store, bool cost) {
-    const dim3 grid((unsigned)wmap_grid(g.m, g.n)), block(256);
-    if (store && cost) hipLaunchKernelGGL((wmap_kernel<MAP, true, true>), grid, block, 0, st, g);
-    else if (store) hipLaunchKernelGGL((wmap_kernel<MAP, true, false>), grid, block, 0, st, g);
-    else hipLaunchKernelGGL((wmap_kernel<MAP, false, true>), grid, block, 0, st, g);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
-}
 
 // ingest: V <- 0 where M == 0 (whatever was there: NaN, Inf, negative), and the constant operand M.*V of the euclidean maps
 __global__ __launch_bounds__(256) void wnmf_prepare(float *V, const float *M, float *MV, long count) {

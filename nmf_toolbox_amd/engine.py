@@ -9,7 +9,8 @@ Multi-GPU: V and H are column-sharded, W is replicated; per ite
 of the packed W-step partials [N | P] (KL: [N | rowsum(H)]).  Everything after the all-reduce is
 computed redundantly and identically on every rank, so W stays bit-identical across ranks.
 
-Single fused passes on torch tensors, at the end of this file: softmask (nmfx_softmask_dev), impute and holdout (nmfx_impute_dev).
+Single fused passes on torch tensors, at the end of this file: softmask (nmfx_softmask_dev), impute and holdout (nmfx_impute_dev); and the weighted fit
+between them, wnmf (nmfx_wnmf_dev).
 """
 from __future__ import annotations
 
@@ -521,13 +522,13 @@ def _real_entry(fn):
     return real
 
 
-def _factors32(fn, Wl, Hl, check, flags):
+def _factors32(fn, Wl, Hl, check, flags, names=("W", "H")):
     """The values of W and H on the fp32 images the device contracts -> ([W_i], [H_i]) as float32 torch tensors.  numpy entries are checked on the host as
     the host calls check them; torch entries where they live: with `check`, a flag pair (not finite, negative) per entry is appended to flags[device], to
     be read back together by _raise_flags (the one synchronisation nmfx_check = False avoids)."""
     import torch
     W32, H32 = [], []
-    for name, src, dst in (("W", Wl, W32), ("H", Hl, H32)):
+    for name, src, dst in ((names[0], Wl, W32), (names[1], Hl, H32)):
         for a in src:
             if isinstance(a, torch.Tensor):
                 a32 = a.to(torch.float32)
@@ -773,3 +774,176 @@ def holdout(V, M, W, H, config=None):
     the scores do not depend on the grid or the stream (the totals need not be the bits of toolbox.holdout, whose sum over the tiles is serial).
     Inputs, config['nmfx_check'] and refusals as for engine.impute; V must be finite everywhere (checked with nmfx_check)."""
     return _impute_dev("engine.holdout", V, M, W, H, config, True)
+
+
+def _wnmf_inits(fn, cfg, Ks, m, n):
+    """W_init / H_init of engine.wnmf -> (validated config, [W_i], [H_i], is_W_cell, is_H_cell): entries given as numpy arrays or torch tensors (any device,
+    any strides) stay what they are, missing ones are the float64 arrays toolbox.wnmf draws for the same seed / rng (toolbox._validate_shape: H first, then W)"""
+    import torch
+    from . import toolbox as TB
+
+    def entries(name):
+        val = cfg.get(name, None)
+        if val is None:
+            return None, False
+        if isinstance(val, torch.Tensor):
+            return ([val], False) if val.numel() else (None, False)
+        if TB._is_cell(val):
+            return (list(val), True) if len(val) else (None, False)
+        return ([val], False) if np.size(val) else (None, False)
+
+    given, cfg2 = {}, dict(cfg)
+    for name in ("W_init", "H_init"):
+        ent, cell = entries(name)
+        given[name] = ent
+        if ent is None:
+            cfg2[name] = None
+        else:                       # stand-ins: _validate_shape counts them, decides list or single, and draws nothing in their place
+            hold = [np.zeros((1, 1)) for _ in ent]
+            cfg2[name] = hold if cell else hold[0]
+    try:
+        cfgv, Wl, Hl, is_W_cell, is_H_cell = TB._validate_shape((m, n), Ks, 1, cfg2, False)
+    except ValueError as e:
+        raise ValueError("%s: %s" % (fn, e)) from None
+    real = _real_entry(fn)
+    Wl = [real(a, "W_init") for a in given["W_init"]] if given["W_init"] is not None else Wl
+    Hl = [real(a, "H_init") for a in given["H_init"]] if given["H_init"] is not None else Hl
+    for s, K in enumerate(Ks):
+        if tuple(Wl[s].shape) != (m, K):
+            raise ValueError("%s: W_init{%d} must be %d-by-%d; got %r" % (fn, s + 1, m, K, tuple(Wl[s].shape)))
+        if tuple(Hl[s].shape) != (K, n):
+            raise ValueError("%s: H_init{%d} must be %d-by-%d; got %r" % (fn, s + 1, K, n, tuple(Hl[s].shape)))
+    return cfgv, Wl, Hl, is_W_cell, is_H_cell
+
+
+def _wnmf_prepare(V, M, num_basis_elems, config):
+    """every check of engine.wnmf and everything the C call is handed that does not need the device, as a dict; nothing here loads the library"""
+    import torch
+    from . import toolbox as TB
+    fn = "engine.wnmf"
+    cfg = config if config else {}
+    div = TB._weighted_config(fn, cfg)
+    check = cfg.get("nmfx_check", True)
+    if not isinstance(check, (bool, np.bool_)):
+        raise ValueError("%s: nmfx_check must be True or False; got %r" % (fn, check))
+    for name, a in (("V", V), ("M", M)):
+        if not isinstance(a, torch.Tensor):
+            raise ValueError("%s: %s must be a torch tensor (the host call wnmf takes arrays); got %s" % (fn, name, type(a).__name__))
+    if V.dim() != 2:
+        raise ValueError("%s: V must be a matrix" % fn)
+    m, n = int(V.shape[0]), int(V.shape[1])
+    if m < 1 or n < 1:
+        raise ValueError("%s: V must not be empty; got %d x %d" % (fn, m, n))
+    if tuple(M.shape) != (m, n):
+        raise ValueError("%s: M must have the shape of V, %r; got %r" % (fn, (m, n), tuple(M.shape)))
+    if V.dtype != torch.float32:
+        raise ValueError("%s: V must be float32 on the device; got %s.  The host call wnmf serves float64 (and every other dtype, as float64); nothing runs "
+                         "silently in another precision" % (fn, V.dtype))
+    if M.dtype not in (torch.float32, torch.bool, torch.uint8):
+        raise ValueError("%s: M must be float32 (weights) or torch.bool / torch.uint8 (a mask: non-zero = observed, weight 1) on the device; got %s -- "
+                         "convert it first (M.float(), or M > 0)" % (fn, M.dtype))
+    fits = _view_layouts(V)
+    for name, a in (("V", V), ("M", M)):
+        if not _view_layouts(a):
+            raise ValueError("%s: %s must have one unit stride and the other at least the extent, without overlap (row-major (ld, 1) with ld >= n, or "
+                             "column-major (1, ld) with ld >= m); got shape %r with strides %r -- pass %s.contiguous()" % (fn, name, (m, n), tuple(a.stride()), name))
+    layout, ldv = next(iter(fits.items()))
+    if M.device != V.device:
+        raise ValueError("%s: M must live on V's device, %s; got %s" % (fn, V.device, M.device))
+    if layout not in _view_layouts(M):
+        raise ValueError("%s: M must be in V's layout class (%s); got strides %r beside V's %r" % (fn, "row-major" if layout else "column-major",
+                                                                                                   tuple(M.stride()), tuple(V.stride())))
+    ldm = _view_layouts(M)[layout]
+    for name, a in (("V", V), ("M", M)):
+        if a.is_conj() or a.is_neg():
+            raise ValueError("%s: %s is a lazy conjugate or negative view: call .resolve_conj() (.resolve_neg()) on it first" % (fn, name))
+    try:
+        Ks = [int(k) for k in (num_basis_elems if TB._is_cell(num_basis_elems) else [num_basis_elems])]
+    except (TypeError, ValueError):
+        raise ValueError("%s: num_basis_elems must be a positive integer or a list of them; got %r" % (fn, num_basis_elems)) from None
+    if not Ks or min(Ks) < 1:
+        raise ValueError("%s: num_basis_elems must be a positive integer or a list of them; got %r" % (fn, num_basis_elems))
+    cfgv, Wl, Hl, is_W_cell, is_H_cell = _wnmf_inits(fn, cfg, Ks, m, n)
+    # the values, where they live: torch inits and a float32 M by flags read back together (the one synchronisation nmfx_check = False avoids), numpy inits
+    # on the host; inits travel as float32, as in the host call with a float32 V
+    flags = {}
+    W32, H32 = _factors32(fn, Wl, Hl, check, flags, names=("W_init", "H_init"))
+    messages = {name: ("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name), "%s: every entry of %s must be >= 0" % (fn, name))
+                for name in ("W_init", "H_init")}
+    messages["M"] = ("%s: every weight in M must be finite" % fn, "%s: every weight in M must be >= 0" % fn)
+    if check and M.dtype == torch.float32:
+        flags.setdefault(M.device, []).append(("M", torch.stack([~torch.isfinite(M).all(), (M < 0).any()])))
+    _raise_flags(flags, messages)
+    rep = lambda key, dt: np.ascontiguousarray(np.repeat(np.asarray(cfgv[key]).astype(dt), Ks))
+    maxiter = int(cfgv["maxiter"])
+    return dict(fn=fn, m=m, n=n, Ks=Ks, K=int(sum(Ks)), div=TB._DIV_WNMF[div], layout=layout, ldv=ldv, ldm=ldm, m_kind=0 if M.dtype == torch.float32 else 1,
+                W32=W32, H32=H32, is_W_cell=is_W_cell, is_H_cell=is_H_cell, maxiter=maxiter,
+                tolerance=-1.0 if cfgv.get("nmfx_disable_stop", False) else float(cfgv["tolerance"]),
+                lamW=rep("W_sparsity", np.float32), lamH=rep("H_sparsity", np.float32), fixW=rep("W_fixed", np.uint8), fixH=rep("H_fixed", np.uint8))
+
+
+def wnmf(V, M, num_basis_elems, config=None):
+    """W, H, cost = engine.wnmf(V, M, num_basis_elems, config): toolbox.wnmf on data that lives on the GPU, on torch's current stream of V's device; the
+    factors and the cost stay there.  Same update equations (csrc/wnmf.hip), the same arithmetic and the same config keys.
+
+    V: a 2-D float32 torch tensor, m x n, with one unit stride and the other at least the extent: row-major (stride (ld, 1), ld >= n: what torch.stft
+    returns per batch entry) or column-major (stride (1, ld), ld >= m); slices of wider / taller tensors are fine and a view may begin at any element.  V is
+    passed by pointer, never copied and never written, and never looked at where M == 0 (NaN, Inf or anything else may stand there).
+    M: a tensor of V's shape on V's device in V's layout class, with its own leading dimension, read in place too: float32 weights (>= 0 and finite), or
+    torch.bool / torch.uint8 (observed where non-zero, weight 1: one byte of traffic per element and pass instead of four).
+    num_basis_elems and config are toolbox.wnmf's: several sources as lists; divergence 'euclidean', 'kl' / 'kl_divergence', 'is' / 'is_divergence';
+    W_sparsity, H_sparsity, W_fixed, H_fixed, maxiter, tolerance, nmfx_disable_stop, seed / rng, W_init, H_init.  Entries of W_init / H_init are numpy
+    arrays or torch tensors on any device with any strides; missing ones are the arrays toolbox.wnmf draws for the same seed.  Inits travel as float32, as
+    in the host call with a float32 V.
+    config['nmfx_check'] (default True): check where they live that torch inits and a float32 M are finite and >= 0, which costs one host synchronisation;
+    False skips the checks and the wait (numpy inits are always checked on the host).
+
+    Returns what toolbox.wnmf returns for a float32 V, as tensors on V's device: W (m x K) and H (K x n) float32, the fp32 images of the float64 masters
+    (lists per source when num_basis_elems is a list), fresh contiguous allocations in V's layout class (column-major: .t() views of contiguous tensors);
+    cost float64, trimmed to the iterations run.  Feed them to engine.holdout / engine.impute with the same V: nothing goes through the host.
+    With the stop rule on the host reads 8 bytes per iteration, as in the host call.  With nmfx_disable_stop=True, nmfx_check=False and inits that are
+    already on V's device the call waits for nothing and all device memory comes from torch: one work buffer of nmfx_wnmf_dev_work_bytes -- 4*m*n bytes
+    for kl with float32 weights (M itself is the second operand), 8*m*n otherwise, plus O((m + n)*K + maxiter) and the GEMM scratch -- against the
+    12*m*n / 16*m*n the host call holds on the device.
+    Refused: what toolbox.wnmf refuses ('ab' and unknown divergences, nmfx_gpus, nmfx_multi_backend, nmfx_precision='float64', M of another shape); a V
+    or M that is not a torch tensor; a V that is not 2-D, is empty or is not float32; M of another dtype, device or layout class; no unit stride, or
+    overlap; lazy conj / neg views.  A CPU tensor that passes every check ends in NmfxError(NMFX_ERR_NO_DEVICE): there is no CPU fallback."""
+    import torch
+    a = _wnmf_prepare(V, M, num_basis_elems, config)
+    fn, m, n, K, Ks, layout = a["fn"], a["m"], a["n"], a["K"], a["Ks"], a["layout"]
+    if not V.is_cuda:
+        raise _lib.NmfxError(_lib.NMFX_ERR_NO_DEVICE, "%s needs a CUDA/HIP tensor V: there is no CPU fallback" % fn)
+    dev = V.device
+    # the float64 inits in the library's layout, W[i + m*k] = a contiguous (K, m) tensor and H[k + K*j] = a contiguous (n, K) one, from the fp32 entries
+    W0 = torch.cat([w.to(dev) for w in a["W32"]], dim=1).t().contiguous().to(torch.float64)
+    H0 = torch.cat([h.to(dev) for h in a["H32"]], dim=0).t().contiguous().to(torch.float64)
+    lib = _lib.load()
+    need = C.c_size_t()
+    _lib.check(lib.nmfx_wnmf_dev_work_bytes(m, n, K, a["div"], a["m_kind"], a["maxiter"], C.byref(need)))
+    work = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    if layout == 1:
+        Wt, Ht = torch.empty((m, K), dtype=torch.float32, device=dev), torch.empty((K, n), dtype=torch.float32, device=dev)
+        W, H = Wt, Ht
+    else:
+        Wt, Ht = torch.empty((K, m), dtype=torch.float32, device=dev), torch.empty((n, K), dtype=torch.float32, device=dev)
+        W, H = Wt.t(), Ht.t()
+    cost = torch.empty(a["maxiter"], dtype=torch.float64, device=dev)
+    iters = C.c_int32(0)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    ptr = lambda arr: arr.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.nmfx_wnmf_dev(stream, m, n, K, a["div"], layout, C.c_void_p(V.data_ptr()), a["ldv"], C.c_void_p(M.data_ptr()), a["ldm"], a["m_kind"],
+                                 ptr(a["lamW"]), ptr(a["lamH"]), ptr(a["fixW"]), ptr(a["fixH"]), C.c_void_p(W0.data_ptr()), C.c_void_p(H0.data_ptr()),
+                                 a["maxiter"], a["tolerance"], C.c_void_p(work.data_ptr()), need.value, C.c_void_p(Wt.data_ptr()), C.c_void_p(Ht.data_ptr()),
+                                 C.c_void_p(cost.data_ptr()), C.byref(iters), index))
+    # (W0, H0 and work go back to torch's allocator when this frame ends: it reuses them in stream order, behind the kernels launched above)
+    cost = cost[: iters.value]
+    if len(Ks) > 1:      # one fresh contiguous tensor per source, in the layout class
+        offs = np.concatenate([[0], np.cumsum(Ks)])
+        cut = (lambda t, lo, hi, rows: (t[lo:hi] if rows else t[:, lo:hi]).contiguous()) if layout == 1 else \
+              (lambda t, lo, hi, rows: (t.t()[:, lo:hi] if rows else t.t()[lo:hi]).contiguous().t())
+        Wl = [cut(W, int(offs[s]), int(offs[s + 1]), False) for s in range(len(Ks))]
+        Hl = [cut(H, int(offs[s]), int(offs[s + 1]), True) for s in range(len(Ks))]
+    else:
+        Wl, Hl = [W], [H]
+    return (Wl if a["is_W_cell"] else Wl[0]), (Hl if a["is_H_cell"] else Hl[0]), cost

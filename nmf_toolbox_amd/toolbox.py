@@ -74,8 +74,13 @@ def _per_source(cfg, name, S, default, conv, what):
 
 def _validate(V, Ks, T, config, cnmf_mode):
     """The local ValidateParameters of nmf.m:238-413 (cnmf_mode False) / cnmf.m:271-449 (True)."""
+    return _validate_shape(V.shape, Ks, T, config, cnmf_mode)
+
+
+def _validate_shape(shape, Ks, T, config, cnmf_mode):
+    """_validate on the shape of V alone (nothing of nmf.m:238-413 reads V's values): what the device calls, whose V is not a host array, share with it"""
     cfg = dict(config) if config else {}
-    m, n = V.shape
+    m, n = shape
     S = len(Ks)
     rng = _rng(cfg)
     if "divergence" not in cfg:                                   # nmf.m:250-252
@@ -265,6 +270,15 @@ _DIV_WNMF = {"euclidean": _lib.DIV_EUCLIDEAN, "kl_divergence": _lib.DIV_KL, "kl"
 def _weighted_inputs(fn, V, M, config):
     """What wnmf and wcnmf check before anything else, with `fn` in every message: the refused extensions, the divergence, V a matrix, M of V's shape and
     of a real kind with finite weights >= 0.  Returns V and M as they travel (M in V's dtype, column-major) and the divergence's name."""
+    div = _weighted_config(fn, config)
+    V = _as_data(V)
+    if V.ndim != 2:
+        raise ValueError("%s: V must be a matrix" % fn)
+    return V, _weights(fn, M, V.shape, V.dtype), div
+
+
+def _weighted_config(fn, config):
+    """the part of _weighted_inputs that reads the config alone (shared with engine.wnmf): the refused extensions and the divergence -> its name"""
     cfg0 = config if config else {}
     try:
         _precision(cfg0, fn)     # (raises for 'float64' / 'double' -- nothing runs silently in another precision -- and for invalid values)
@@ -277,10 +291,7 @@ def _weighted_inputs(fn, V, M, config):
         raise ValueError("%s has no alpha-beta divergence: its divergences are 'euclidean', 'kl' ('kl_divergence') and 'is' ('is_divergence')" % fn)
     if not isinstance(div, str) or div not in _DIV_WNMF:
         raise ValueError("%s: no update equations defined for cost function with divergence type %s" % (fn, div))
-    V = _as_data(V)
-    if V.ndim != 2:
-        raise ValueError("%s: V must be a matrix" % fn)
-    return V, _weights(fn, M, V.shape, V.dtype), div
+    return div
 
 
 def _weights(fn, M, shape, dtype, name="M", of="V"):
