@@ -44,6 +44,22 @@ struct Carver {
     }
 };
 
+// What the device-resident entries (nmfx_softmask_dev, nmfx_impute_dev, nmfx_wnmf_dev) refuse of a view, one text each; `fn` is the entry's name, `name`
+// the argument's.  A leading dimension must reach the contiguous extent `lead`, and, with `other` (the extent it steps over) given, ld * other must fit.
+inline nmfx_status view_layout(const char *fn, int layout) {
+    if (layout == 0 || layout == 1) return NMFX_OK;
+    set_error("%s: layout = %d: 0 (column-major) or 1 (row-major)", fn, layout); return NMFX_ERR_INVALID;
+}
+inline nmfx_status view_m_kind(const char *fn, int m_kind) {
+    if (m_kind == 0 || m_kind == 1) return NMFX_OK;
+    set_error("%s: m_kind = %d: 0 (float32 weights) or 1 (bytes)", fn, m_kind); return NMFX_ERR_INVALID;
+}
+inline nmfx_status view_ld(const char *fn, const char *name, int64_t ld, int64_t lead, int64_t other = 0) {
+    if (ld < lead) { set_error("%s: %s = %lld is below the contiguous extent %lld", fn, name, (long long)ld, (long long)lead); return NMFX_ERR_INVALID; }
+    if (other > 0 && ld > (INT64_MAX / 8 - lead) / other) { set_error("%s: %s = %lld times %lld does not fit", fn, name, (long long)ld, (long long)other); return NMFX_ERR_INVALID; }
+    return NMFX_OK;
+}
+
 // grid.y of a fused pass over `blocks` 128-row blocks (engine.hip)
 int fused_split(long blocks, long extent, int K, long *c_per_split);
 

@@ -81,17 +81,14 @@ extern "C" nmfx_status nmfx_impute_dev(void *stream, int64_t m, int64_t n, int32
     if ((Y_dev != nullptr) == (scores_dev != nullptr)) {
         set_error("nmfx_impute_dev: exactly one of Y_dev (fill) and scores_dev (score) must be given; got %s", Y_dev ? "both" : "neither"); return NMFX_ERR_INVALID;
     }
-    if (layout != 0 && layout != 1) { set_error("nmfx_impute_dev: layout = %d: 0 (column-major) or 1 (row-major)", layout); return NMFX_ERR_INVALID; }
-    if (m_kind != 0 && m_kind != 1) { set_error("nmfx_impute_dev: m_kind = %d: 0 (float32 weights) or 1 (bytes)", m_kind); return NMFX_ERR_INVALID; }
+    TRY(view_layout("nmfx_impute_dev", layout));
+    TRY(view_m_kind("nmfx_impute_dev", m_kind));
     if (frames != 0 && frames != 1) { set_error("nmfx_impute_dev: frames = %d: 0 (totals) or 1 (one pair of scores per column)", frames); return NMFX_ERR_INVALID; }
     if (frames && Y_dev) { set_error("nmfx_impute_dev: frames belongs to the scores; a fill (Y_dev) has none"); return NMFX_ERR_INVALID; }
     const int64_t lead = layout == 0 ? m : n, other = layout == 0 ? n : m;   // the contiguous extent, and the one the leading dimension steps over
-    const struct { const char *name; int64_t ld; bool used; } lds[3] = {{"ldv", ldv, true}, {"ldm", ldm, true}, {"ldy", ldy, Y_dev != nullptr}};
-    for (const auto &l : lds) {
-        if (!l.used) continue;
-        if (l.ld < lead) { set_error("nmfx_impute_dev: %s = %lld is below the contiguous extent %lld", l.name, (long long)l.ld, (long long)lead); return NMFX_ERR_INVALID; }
-        if (l.ld > (INT64_MAX / 8 - lead) / other) { set_error("nmfx_impute_dev: %s = %lld times %lld does not fit", l.name, (long long)l.ld, (long long)other); return NMFX_ERR_INVALID; }
-    }
+    TRY(view_ld("nmfx_impute_dev", "ldv", ldv, lead, other));
+    TRY(view_ld("nmfx_impute_dev", "ldm", ldm, lead, other));
+    if (Y_dev) TRY(view_ld("nmfx_impute_dev", "ldy", ldy, lead, other));
     if (divergence == NMFX_DIV_AB) { set_error("nmfx_impute_dev: the alpha-beta divergence is not supported (euclidean, kl, is)"); return NMFX_ERR_UNSUPPORTED; }
     int div = IMP_NONE;
     size_t need = 0;

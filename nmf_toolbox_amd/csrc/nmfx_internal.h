@@ -332,6 +332,35 @@ nmfx_status f2d(hipStream_t st, const float *in, double *out, int count);
 nmfx_status cvt_to_f32(hipStream_t st, const void *in, int dtype, float *out, long count, double divide_by);
 nmfx_status cvt_to_f64(hipStream_t st, const float *in, double *out, long count);
 
+// ---- wnmf (wnmf.hip): the one driver behind nmfx_wnmf (wnmf.hip) and nmfx_wnmf_dev (wnmf_dev.hip) ----
+// An entry checks its arguments, carves a WnmfWork, fills the masters W64 / H64 with their fp32 images W / H and the vectors lam / fix ([0, K): W's,
+// [K, 2K): H's), runs wnmf_constants and then wnmf_iterate on its stream, and carries W, H and cost[0, iters_run) out its own way.
+enum WMap { WM_EUC = 0, WM_KL = 1, WM_IS = 2 };
+int wnmf_map_of(int divergence);   // the WMap of an NMFX_DIV_*; -1: the divergence has no update equations here
+inline bool wnmf_own_b(int map, int m_kind) { return map != WM_KL || m_kind != 0; }   // (kl with float32 weights: the second operand is M itself)
+struct WnmfCall {
+    long m, n;
+    int K, map;
+    const float *V;        // the view of (V, M): m x n, layout 0 column-major V[i + ldv*j], 1 row-major V[i*ldv + j]; read in place, never written
+    const void *M;         // m_kind 0: float32 weights, 1: bytes (observed where non-zero, weight 1); V's layout, leading dimension ldm
+    long ldv, ldm;
+    int layout, m_kind;
+    bool all_wf, all_hf, any_lw, any_lh;   // over the K components: every W (H) fixed, any lambda_W (lambda_H) non-zero
+    int maxiter;
+    double tolerance;      // < 0: no stop rule, and then nothing waits for the stream
+};
+struct WnmfWork {          // the carve of one work buffer; with base == NULL only `bytes` is computed.  gscratch: what gemm_auto may use (>= gemm_scratch_bytes)
+    float *A, *B, *W, *H, *Nw, *Pw, *Nh, *Ph;   // A, B: the mapped operands in V's layout, packed (B is NULL where wnmf_own_b says so)
+    double *W64, *H64, *parts, *vecs, *cost;
+    void *scr, *rrs;
+    float *lam;
+    uint8_t *fix;
+    size_t gscratch, bytes;
+    WnmfWork(void *base, long m, long n, int K, int map, int m_kind, int maxiter, size_t gscratch);
+};
+nmfx_status wnmf_constants(hipStream_t st, const WnmfCall &c, const WnmfWork &wk);               // the operands no pass rewrites; selects on M, never writes V
+nmfx_status wnmf_iterate(hipStream_t st, const WnmfCall &c, const WnmfWork &wk, int *iters_run);   // -> W64, H64, W, H, cost[0, *iters_run)
+
 // ---- Hoyer projection (projfunc.hip): vectors are the COLUMNS of X (len x count), in place ----
 // dir (or dir64, the direction as doubles) != nullptr: the vectors projected are src + mu*dir, formed in fp64 (the line-search step of
 // nmfsc.m:154 / 205 fused into the load); src == nullptr means X itself.  X receives the result.

@@ -44,14 +44,14 @@ extern "C" nmfx_status nmfx_softmask_dev(void *stream, int64_t m, int64_t n, int
     if (m <= 0 || n <= 0 || I <= 0 || K <= 0 || T <= 0 || !koff_dev || !W_dev || !H_dev || !Y_dev) {
         set_error("nmfx_softmask_dev: bad arguments (sizes must be positive, koff_dev, W_dev, H_dev and Y_dev are required)"); return NMFX_ERR_INVALID;
     }
-    if (layout != 0 && layout != 1) { set_error("nmfx_softmask_dev: layout = %d: 0 (column-major) or 1 (row-major)", layout); return NMFX_ERR_INVALID; }
+    TRY(view_layout("nmfx_softmask_dev", layout));
     if (output != 0 && output != 1) { set_error("nmfx_softmask_dev: output = %d: 0 (estimates) or 1 (masks)", output); return NMFX_ERR_INVALID; }
     if (output == 0 && !X_dev) { set_error("nmfx_softmask_dev: X_dev is required for estimates"); return NMFX_ERR_INVALID; }
     if (!(power > 0.0) || !std::isfinite(power)) { set_error("nmfx_softmask_dev: power must be positive and finite"); return NMFX_ERR_INVALID; }
     if (K < I || K > (1 << 24)) { set_error("nmfx_softmask_dev: K = %d must be at least num_sources = %d and at most 2^24", K, I); return NMFX_ERR_INVALID; }
     const int64_t lead = layout == 0 ? m : n, other = layout == 0 ? n : m;   // the contiguous extent, and the one the leading dimension steps over
-    if (output == 0 && ldx < lead) { set_error("nmfx_softmask_dev: ldx = %lld is below the contiguous extent %lld", (long long)ldx, (long long)lead); return NMFX_ERR_INVALID; }
-    if (ldy < lead) { set_error("nmfx_softmask_dev: ldy = %lld is below the contiguous extent %lld", (long long)ldy, (long long)lead); return NMFX_ERR_INVALID; }
+    if (output == 0) TRY(view_ld("nmfx_softmask_dev", "ldx", ldx, lead));
+    TRY(view_ld("nmfx_softmask_dev", "ldy", ldy, lead));   // (ldy * other: bounded with y_slab below)
     if (ldy > (INT64_MAX - lead) / other || y_slab < ldy * (other - 1) + lead) {
         set_error("nmfx_softmask_dev: y_slab = %lld is too small for one output (ldy * %lld + %lld elements)", (long long)y_slab, (long long)(other - 1), (long long)lead);
         return NMFX_ERR_INVALID;

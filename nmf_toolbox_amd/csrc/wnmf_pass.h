@@ -1,7 +1,6 @@
-// The weighted map pass of wnmf (definition: wnmf.hip's head) as a template of what differs between its two entries: the host entry nmfx_wnmf
-// (wnmf.hip: its own packed column-major fp32 copies of V and M) and the device entry nmfx_wnmf_dev (wnmf_dev.hip: the caller's tensors read in place, both
-// layouts, leading dimensions, byte masks).
-//   ARGS: WMapArgs (nmfx_wnmf: every leading dimension is m, as before the pass had views) or WMapDevArgs (views with ldv, ldm, lda).
+// The weighted map pass of wnmf (definition and schedule: wnmf.hip's head), a template over the layout of V / M and the element of M.  Both
+// entries run it from the one driver (wnmf.hip, the only translation unit that includes this file): nmfx_wnmf on its packed column-major fp32 copies
+// (LAYOUT 0, float, every leading dimension m), nmfx_wnmf_dev on the caller's tensors read in place.
 //   LAYOUT 0, column-major: element (i, j) of V at V[i + ldv*j] (M with ldm; A and B with lda).  The MFMA is fed transposed (first operand the H stage, second
 //       W), so a lane of the accumulator holds one row i and 16 columns: every access to V, M, A and B is 32 consecutive elements of a column.
 //   LAYOUT 1, row-major: element (i, j) at V[i*ldv + j].  The operands change places (first W, second the H stage): a lane holds one column j and 16 rows,
@@ -19,34 +18,18 @@
 namespace nmfx {
 namespace {
 
-enum WMap { WM_EUC = 0, WM_KL = 1, WM_IS = 2 };
-
 constexpr int WBM = 128, WBN = 64, WBK = 16, WLDH = WBK + 1;
 constexpr int WMAP_MAX_GRID = 8192;
 
-struct WMapArgs {           // nmfx_wnmf: packed column-major, every leading dimension is m
+struct WMapDevArgs {        // views of V and M with their own leading dimensions
     const float *W, *H;     // fp32 images: W[i + m*k], H[k + K*j]
-    const float *V, *M;     // m x n
-    float *A, *B;           // m x n outputs of a storing pass (either may be NULL: not needed by the divergence)
+    const float *V;         // m x n view, leading dimension ldv
+    const void *M;          // m x n view of MT, leading dimension ldm
+    float *A, *B;           // m x n outputs of a storing pass in V's layout, leading dimension lda (either may be NULL: not needed by the divergence)
     long m, n;
     int K;
+    long ldv, ldm, lda;
     double *partials;       // [gridDim.x] weighted data-fit partials of a cost pass
-    __device__ long ldv() const { return m; }
-    __device__ long ldm() const { return m; }
-    __device__ long lda() const { return m; }
-};
-struct WMapDevArgs {        // nmfx_wnmf_dev: views of the caller's tensors with their own leading dimensions
-    const float *W, *H;     // fp32 images: W[i + m*k], H[k + K*j]
-    const float *V;         // m x n view, leading dimension ldv_
-    const void *M;          // m x n view of MT, leading dimension ldm_
-    float *A, *B;           // m x n outputs of a storing pass in V's layout, leading dimension lda_
-    long m, n;
-    int K;
-    long ldv_, ldm_, lda_;
-    double *partials;
-    __device__ long ldv() const { return ldv_; }
-    __device__ long ldm() const { return ldm_; }
-    __device__ long lda() const { return lda_; }
 };
 
 template <class MT> struct WWeight {   // a weight: observed where it is positive
@@ -58,8 +41,8 @@ template <> struct WWeight<unsigned char> {   // a byte of a bool / uint8 mask: 
     static __device__ __forceinline__ float value(unsigned char) { return 1.0f; }
 };
 
-template <int MAP, bool STORE, bool COST, int LAYOUT = 0, class MT = float, class ARGS = WMapArgs>
-__global__ __launch_bounds__(256, 2) void wmap_kernel(const ARGS g) {
+template <int MAP, bool STORE, bool COST, int LAYOUT, class MT>
+__global__ __launch_bounds__(256, 2) void wmap_kernel(const WMapDevArgs g) {
     constexpr bool NEED_V = COST || MAP != WM_EUC;   // the storing euclidean pass forms B = M.*S only
     typedef MT m16t __attribute__((ext_vector_type(16)));
     __shared__ float Ws[2][WBK * WBM];
@@ -126,12 +109,12 @@ __global__ __launch_bounds__(256, 2) void wmap_kernel(const ARGS g) {
                 at(y, e, r, j);
                 const long jc = j < g.n ? j : g.n - 1;
                 if constexpr (LAYOUT == 0) {
-                    mreg[y][e] = Mp[ic + g.ldm() * jc];
-                    vreg[y][e] = NEED_V ? g.V[ic + g.ldv() * jc] : 0.0f;
+                    mreg[y][e] = Mp[ic + g.ldm * jc];
+                    vreg[y][e] = NEED_V ? g.V[ic + g.ldv * jc] : 0.0f;
                 } else {
                     const long rc = r < g.m ? r : g.m - 1;
-                    mreg[y][e] = Mp[rc * g.ldm() + jc];
-                    vreg[y][e] = NEED_V ? g.V[rc * g.ldv() + jc] : 0.0f;
+                    mreg[y][e] = Mp[rc * g.ldm + jc];
+                    vreg[y][e] = NEED_V ? g.V[rc * g.ldv + jc] : 0.0f;
                 }
             }
         __builtin_amdgcn_sched_barrier(0);   // (or the compiler sinks every one of them to its first use)
@@ -167,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void wmap_kernel(const ARGS g) {
                 at(y, e, r, j);
                 const float s = s16[e], v = v16[e], w = WWeight<MT>::value(m16[e]);
                 const bool inside = r < g.m && j < g.n, on = WWeight<MT>::on(m16[e]) && inside;
-                const long idx = LAYOUT == 0 ? r + g.lda() * j : r * g.lda() + j;
+                const long idx = LAYOUT == 0 ? r + g.lda * j : r * g.lda + j;
                 if constexpr (STORE) {
                     if (inside) {
                         if constexpr (MAP == WM_EUC) g.B[idx] = on ? w * s : 0.0f;
@@ -194,12 +177,12 @@ __global__ __launch_bounds__(256, 2) void wmap_kernel(const ARGS g) {
 
 inline long wmap_grid(long m, long n) { return std::min<long>(((m + WBM - 1) / WBM) * ((n + WBN - 1) / WBN), WMAP_MAX_GRID); }
 
-template <int MAP, int LAYOUT = 0, class MT = float, class ARGS = WMapArgs>
-nmfx_status wmap_launch(hipStream_t st, const ARGS &g, bool store, bool cost) {
+template <int MAP, int LAYOUT, class MT>
+nmfx_status wmap_launch(hipStream_t st, const WMapDevArgs &g, bool store, bool cost) {
     const dim3 grid((unsigned)wmap_grid(g.m, g.n)), block(256);
-    if (store && cost) hipLaunchKernelGGL((wmap_kernel<MAP, true, true, LAYOUT, MT, ARGS>), grid, block, 0, st, g);
-    else if (store) hipLaunchKernelGGL((wmap_kernel<MAP, true, false, LAYOUT, MT, ARGS>), grid, block, 0, st, g);
-    else hipLaunchKernelGGL((wmap_kernel<MAP, false, true, LAYOUT, MT, ARGS>), grid, block, 0, st, g);
+    if (store && cost) hipLaunchKernelGGL((wmap_kernel<MAP, true, true, LAYOUT, MT>), grid, block, 0, st, g);
+    else if (store) hipLaunchKernelGGL((wmap_kernel<MAP, true, false, LAYOUT, MT>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL((wmap_kernel<MAP, false, true, LAYOUT, MT>), grid, block, 0, st, g);
     NMFX_HIP(hipGetLastError());
     return NMFX_OK;
 }

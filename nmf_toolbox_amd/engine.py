@@ -558,9 +558,25 @@ def _raise_flags(flags, messages):
                 raise ValueError(messages[name][1])
 
 
-def _factor_messages(fn):
+def _factor_messages(fn, names=("W", "H")):
     return {name: ("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name), "%s: every entry of %s must be >= 0" % (fn, name))
-            for name in ("W", "H")}
+            for name in names}
+
+
+def _nmfx_check(fn, cfg):
+    """config['nmfx_check'] of the device calls (default True)"""
+    check = cfg.get("nmfx_check", True)
+    if not isinstance(check, (bool, np.bool_)):
+        raise ValueError("%s: nmfx_check must be True or False; got %r" % (fn, check))
+    return check
+
+
+def _weight_flags(fn, M, check, flags, messages):
+    """the values of a float32 M, where it lives: its flag pair joins `flags` (with `check`) and its two messages `messages`"""
+    import torch
+    messages["M"] = ("%s: every weight in M must be finite" % fn, "%s: every weight in M must be >= 0" % fn)
+    if check and M.dtype == torch.float32:
+        flags.setdefault(M.device, []).append(("M", torch.stack([~torch.isfinite(M).all(), (M < 0).any()])))
 
 
 def _view_layouts(t):
@@ -578,6 +594,65 @@ def _view_layouts(t):
     if row_ok and 1 not in out:
         out[1] = s0 if m > 1 else n
     return out
+
+
+def _unit_stride_layouts(fn, name, t):
+    """_view_layouts(t), or the refusal of a tensor that fits neither layout"""
+    fits = _view_layouts(t)
+    if not fits:
+        raise ValueError("%s: %s must have one unit stride and the other at least the extent, without overlap (row-major (ld, 1) with ld >= n, or column-major "
+                         "(1, ld) with ld >= m); got shape %r with strides %r -- pass %s.contiguous()" % (fn, name, tuple(t.shape), tuple(t.stride()), name))
+    return fits
+
+
+def _no_lazy_view(fn, name, t):
+    if t.is_conj() or t.is_neg():
+        raise ValueError("%s: %s is a lazy conjugate or negative view: call .resolve_conj() (.resolve_neg()) on it first" % (fn, name))
+
+
+def _vm_shape(fn, V, M, real):
+    """First stage of the one V / M check of engine.impute, engine.holdout and engine.wnmf: both torch tensors, V a non-empty matrix, M of its shape -> m, n.
+    `real` (impute, holdout): a complex or otherwise non-real V or M is refused here, before the float32 messages of _vm_view."""
+    import torch
+    host = fn.split(".")[-1]
+    for name, a in (("V", V), ("M", M)):
+        if not isinstance(a, torch.Tensor):
+            raise ValueError("%s: %s must be a torch tensor (the host call %s takes arrays); got %s" % (fn, name, host, type(a).__name__))
+    if V.dim() != 2:
+        raise ValueError("%s: V must be a matrix" % fn)
+    real_kinds = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+    if real and (V.is_complex() or not (V.is_floating_point() or V.dtype in real_kinds)):
+        raise ValueError("%s: V must be real (bool, integer or float); got %s" % (fn, V.dtype))
+    m, n = int(V.shape[0]), int(V.shape[1])
+    if m < 1 or n < 1:
+        raise ValueError("%s: V must not be empty; got %d x %d" % (fn, m, n))
+    if tuple(M.shape) != (m, n):
+        raise ValueError("%s: M must have the shape of V, %r; got %r" % (fn, (m, n), tuple(M.shape)))
+    if real and (M.is_complex() or not (M.is_floating_point() or M.dtype in real_kinds)):
+        raise ValueError("%s: M must be bool, integer or float; got %s" % (fn, M.dtype))
+    return m, n
+
+
+def _vm_view(fn, V, M):
+    """Second stage: the dtypes the device reads, one layout class for both, one device, no lazy views -> layout, ldv, ldm, m_kind as the C entries take them"""
+    import torch
+    host = fn.split(".")[-1]
+    if V.dtype != torch.float32:
+        raise ValueError("%s: V must be float32 on the device; got %s.  The host call %s serves float64 (and every other dtype, as float64); nothing runs "
+                         "silently in another precision" % (fn, V.dtype, host))
+    if M.dtype not in (torch.float32, torch.bool, torch.uint8):
+        raise ValueError("%s: M must be float32 (weights) or torch.bool / torch.uint8 (a mask: non-zero = observed, weight 1) on the device; got %s -- "
+                         "convert it first (M.float(), or M > 0)" % (fn, M.dtype))
+    fits, fits_m = _unit_stride_layouts(fn, "V", V), _unit_stride_layouts(fn, "M", M)
+    layout, ldv = next(iter(fits.items()))
+    if M.device != V.device:
+        raise ValueError("%s: M must live on V's device, %s; got %s" % (fn, V.device, M.device))
+    if layout not in fits_m:
+        raise ValueError("%s: M must be in V's layout class (%s); got strides %r beside V's %r" % (fn, "row-major" if layout else "column-major",
+                                                                                                   tuple(M.stride()), tuple(V.stride())))
+    _no_lazy_view(fn, "V", V)
+    _no_lazy_view(fn, "M", M)
+    return layout, ldv, fits_m[layout], 0 if M.dtype == torch.float32 else 1
 
 
 def softmask(X, W, H, config=None):
@@ -599,9 +674,7 @@ def softmask(X, W, H, config=None):
     fn = "engine.softmask"
     cfg = config if config else {}
     power, masks = TB._softmask_config(fn, cfg)
-    check = cfg.get("nmfx_check", True)
-    if not isinstance(check, (bool, np.bool_)):
-        raise ValueError("%s: nmfx_check must be True or False; got %r" % (fn, check))
+    check = _nmfx_check(fn, cfg)
     if not isinstance(X, torch.Tensor):
         raise ValueError("%s: X must be a torch tensor (the host call softmask takes arrays); got %s" % (fn, type(X).__name__))
     if X.dim() != 2:
@@ -620,15 +693,8 @@ def softmask(X, W, H, config=None):
     if X.dtype not in (torch.float32, torch.complex64):
         raise ValueError("%s: X must be float32 or complex64 on the device; got %s.  The host call softmask serves float64 / complex128 (and every other "
                          "dtype, as float64); nothing runs silently in another precision" % (fn, X.dtype))
-    s0, s1 = int(X.stride(0)), int(X.stride(1))
-    fits = _view_layouts(X)
-    if fits:
-        layout, ld = next(iter(fits.items()))
-    else:
-        raise ValueError("%s: X must have one unit stride and the other at least the extent, without overlap (row-major (ld, 1) with ld >= n, or column-major "
-                         "(1, ld) with ld >= m); got shape %r with strides %r -- pass X.contiguous()" % (fn, (m, n), (s0, s1)))
-    if X.is_conj() or X.is_neg():
-        raise ValueError("%s: X is a lazy conjugate or negative view: call .resolve_conj() (.resolve_neg()) on it first" % fn)
+    layout, ld = next(iter(_unit_stride_layouts(fn, "X", X).items()))
+    _no_lazy_view(fn, "X", X)
     if not X.is_cuda:
         raise _lib.NmfxError(_lib.NMFX_ERR_NO_DEVICE, "engine.softmask needs a CUDA/HIP tensor X: there is no CPU fallback")
     dev, I, K = X.device, len(Ks), int(sum(Ks))
@@ -655,12 +721,9 @@ def _impute_dev(fn, V, M, W, H, config, scores):
     """engine.impute (scores False) and engine.holdout (scores True): the checks, the two fp32 images, the one call into nmfx_impute_dev"""
     import torch
     from . import toolbox as TB
-    host = fn.split(".")[-1]
     cfg = config if config else {}
     div = TB._impute_config(fn, cfg, scores)
-    check = cfg.get("nmfx_check", True)
-    if not isinstance(check, (bool, np.bool_)):
-        raise ValueError("%s: nmfx_check must be True or False; got %r" % (fn, check))
+    check = _nmfx_check(fn, cfg)
     frames = False
     if "frames" in cfg:
         if not scores:
@@ -669,54 +732,17 @@ def _impute_dev(fn, V, M, W, H, config, scores):
         if not isinstance(frames, (bool, np.bool_)):
             raise ValueError("%s: frames must be True or False; got %r" % (fn, frames))
         frames = bool(frames)
-    for name, a in (("V", V), ("M", M)):
-        if not isinstance(a, torch.Tensor):
-            raise ValueError("%s: %s must be a torch tensor (the host call %s takes arrays); got %s" % (fn, name, host, type(a).__name__))
-    if V.dim() != 2:
-        raise ValueError("%s: V must be a matrix" % fn)
-    real_kinds = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
-    if V.is_complex() or not (V.is_floating_point() or V.dtype in real_kinds):
-        raise ValueError("%s: V must be real (bool, integer or float); got %s" % (fn, V.dtype))
-    m, n = int(V.shape[0]), int(V.shape[1])
-    if m < 1 or n < 1:
-        raise ValueError("%s: V must not be empty; got %d x %d" % (fn, m, n))
-    if tuple(M.shape) != (m, n):
-        raise ValueError("%s: M must have the shape of V, %r; got %r" % (fn, (m, n), tuple(M.shape)))
-    if M.is_complex() or not (M.is_floating_point() or M.dtype in real_kinds):
-        raise ValueError("%s: M must be bool, integer or float; got %s" % (fn, M.dtype))
+    m, n = _vm_shape(fn, V, M, True)
     Wl, Hl, T = TB._impute_factor_shapes(fn, W, H, m, n, entry=_real_entry(fn))
     flags = {}
     W32, H32 = _factors32(fn, Wl, Hl, check, flags)
-    if V.dtype != torch.float32:
-        raise ValueError("%s: V must be float32 on the device; got %s.  The host call %s serves float64 (and every other dtype, as float64); nothing runs "
-                         "silently in another precision" % (fn, V.dtype, host))
-    if M.dtype not in (torch.float32, torch.bool, torch.uint8):
-        raise ValueError("%s: M must be float32 (weights) or torch.bool / torch.uint8 (a mask: non-zero = observed, weight 1) on the device; got %s -- "
-                         "convert it first (M.float(), or M > 0)" % (fn, M.dtype))
-    fits = _view_layouts(V)
-    for name, a in (("V", V), ("M", M)):
-        if not _view_layouts(a):
-            raise ValueError("%s: %s must have one unit stride and the other at least the extent, without overlap (row-major (ld, 1) with ld >= n, or "
-                             "column-major (1, ld) with ld >= m); got shape %r with strides %r -- pass %s.contiguous()" % (fn, name, (m, n), tuple(a.stride()), name))
-    layout, ldv = next(iter(fits.items()))
-    if M.device != V.device:
-        raise ValueError("%s: M must live on V's device, %s; got %s" % (fn, V.device, M.device))
-    if layout not in _view_layouts(M):
-        raise ValueError("%s: M must be in V's layout class (%s); got strides %r beside V's %r" % (fn, "row-major" if layout else "column-major",
-                                                                                                   tuple(M.stride()), tuple(V.stride())))
-    ldm = _view_layouts(M)[layout]
-    for name, a in (("V", V), ("M", M)):
-        if a.is_conj() or a.is_neg():
-            raise ValueError("%s: %s is a lazy conjugate or negative view: call .resolve_conj() (.resolve_neg()) on it first" % (fn, name))
+    layout, ldv, ldm, m_kind = _vm_view(fn, V, M)
     # the values, where they live: W and H (above), a float32 M, and for the scores V; all flags of a device are read back together
     messages = _factor_messages(fn)
-    messages["M"] = ("%s: every weight in M must be finite" % fn, "%s: every weight in M must be >= 0" % fn)
+    _weight_flags(fn, M, check, flags, messages)
     messages["V"] = ("%s: every entry of V must be finite: the hidden entries must be known to be scored (V is read where M == 0 too)" % fn, "")
-    if check:
-        if M.dtype == torch.float32:
-            flags.setdefault(M.device, []).append(("M", torch.stack([~torch.isfinite(M).all(), (M < 0).any()])))
-        if scores:
-            flags.setdefault(V.device, []).append(("V", torch.stack([~torch.isfinite(V).all(), torch.zeros((), dtype=torch.bool, device=V.device)])))
+    if check and scores:
+        flags.setdefault(V.device, []).append(("V", torch.stack([~torch.isfinite(V).all(), torch.zeros((), dtype=torch.bool, device=V.device)])))
     _raise_flags(flags, messages)
     if not V.is_cuda:
         raise _lib.NmfxError(_lib.NMFX_ERR_NO_DEVICE, "%s needs a CUDA/HIP tensor V: there is no CPU fallback" % fn)
@@ -726,7 +752,6 @@ def _impute_dev(fn, V, M, W, H, config, scores):
     lib = _lib.load()
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     index = dev.index if dev.index is not None else torch.cuda.current_device()
-    m_kind = 0 if M.dtype == torch.float32 else 1
     common = (stream, m, n, K, T, layout, C.c_void_p(V.data_ptr()), ldv, C.c_void_p(M.data_ptr()), ldm, m_kind, C.c_void_p(Wimg.data_ptr()),
               C.c_void_p(Himg.data_ptr()))
     if not scores:
@@ -823,40 +848,9 @@ def _wnmf_prepare(V, M, num_basis_elems, config):
     fn = "engine.wnmf"
     cfg = config if config else {}
     div = TB._weighted_config(fn, cfg)
-    check = cfg.get("nmfx_check", True)
-    if not isinstance(check, (bool, np.bool_)):
-        raise ValueError("%s: nmfx_check must be True or False; got %r" % (fn, check))
-    for name, a in (("V", V), ("M", M)):
-        if not isinstance(a, torch.Tensor):
-            raise ValueError("%s: %s must be a torch tensor (the host call wnmf takes arrays); got %s" % (fn, name, type(a).__name__))
-    if V.dim() != 2:
-        raise ValueError("%s: V must be a matrix" % fn)
-    m, n = int(V.shape[0]), int(V.shape[1])
-    if m < 1 or n < 1:
-        raise ValueError("%s: V must not be empty; got %d x %d" % (fn, m, n))
-    if tuple(M.shape) != (m, n):
-        raise ValueError("%s: M must have the shape of V, %r; got %r" % (fn, (m, n), tuple(M.shape)))
-    if V.dtype != torch.float32:
-        raise ValueError("%s: V must be float32 on the device; got %s.  The host call wnmf serves float64 (and every other dtype, as float64); nothing runs "
-                         "silently in another precision" % (fn, V.dtype))
-    if M.dtype not in (torch.float32, torch.bool, torch.uint8):
-        raise ValueError("%s: M must be float32 (weights) or torch.bool / torch.uint8 (a mask: non-zero = observed, weight 1) on the device; got %s -- "
-                         "convert it first (M.float(), or M > 0)" % (fn, M.dtype))
-    fits = _view_layouts(V)
-    for name, a in (("V", V), ("M", M)):
-        if not _view_layouts(a):
-            raise ValueError("%s: %s must have one unit stride and the other at least the extent, without overlap (row-major (ld, 1) with ld >= n, or "
-                             "column-major (1, ld) with ld >= m); got shape %r with strides %r -- pass %s.contiguous()" % (fn, name, (m, n), tuple(a.stride()), name))
-    layout, ldv = next(iter(fits.items()))
-    if M.device != V.device:
-        raise ValueError("%s: M must live on V's device, %s; got %s" % (fn, V.device, M.device))
-    if layout not in _view_layouts(M):
-        raise ValueError("%s: M must be in V's layout class (%s); got strides %r beside V's %r" % (fn, "row-major" if layout else "column-major",
-                                                                                                   tuple(M.stride()), tuple(V.stride())))
-    ldm = _view_layouts(M)[layout]
-    for name, a in (("V", V), ("M", M)):
-        if a.is_conj() or a.is_neg():
-            raise ValueError("%s: %s is a lazy conjugate or negative view: call .resolve_conj() (.resolve_neg()) on it first" % (fn, name))
+    check = _nmfx_check(fn, cfg)
+    m, n = _vm_shape(fn, V, M, False)
+    layout, ldv, ldm, m_kind = _vm_view(fn, V, M)
     try:
         Ks = [int(k) for k in (num_basis_elems if TB._is_cell(num_basis_elems) else [num_basis_elems])]
     except (TypeError, ValueError):
@@ -868,15 +862,12 @@ def _wnmf_prepare(V, M, num_basis_elems, config):
     # on the host; inits travel as float32, as in the host call with a float32 V
     flags = {}
     W32, H32 = _factors32(fn, Wl, Hl, check, flags, names=("W_init", "H_init"))
-    messages = {name: ("%s: every entry of %s must be finite (also once rounded to float32)" % (fn, name), "%s: every entry of %s must be >= 0" % (fn, name))
-                for name in ("W_init", "H_init")}
-    messages["M"] = ("%s: every weight in M must be finite" % fn, "%s: every weight in M must be >= 0" % fn)
-    if check and M.dtype == torch.float32:
-        flags.setdefault(M.device, []).append(("M", torch.stack([~torch.isfinite(M).all(), (M < 0).any()])))
+    messages = _factor_messages(fn, names=("W_init", "H_init"))
+    _weight_flags(fn, M, check, flags, messages)
     _raise_flags(flags, messages)
     rep = lambda key, dt: np.ascontiguousarray(np.repeat(np.asarray(cfgv[key]).astype(dt), Ks))
     maxiter = int(cfgv["maxiter"])
-    return dict(fn=fn, m=m, n=n, Ks=Ks, K=int(sum(Ks)), div=TB._DIV_WNMF[div], layout=layout, ldv=ldv, ldm=ldm, m_kind=0 if M.dtype == torch.float32 else 1,
+    return dict(fn=fn, m=m, n=n, Ks=Ks, K=int(sum(Ks)), div=TB._DIV_WNMF[div], layout=layout, ldv=ldv, ldm=ldm, m_kind=m_kind,
                 W32=W32, H32=H32, is_W_cell=is_W_cell, is_H_cell=is_H_cell, maxiter=maxiter,
                 tolerance=-1.0 if cfgv.get("nmfx_disable_stop", False) else float(cfgv["tolerance"]),
                 lamW=rep("W_sparsity", np.float32), lamH=rep("H_sparsity", np.float32), fixW=rep("W_fixed", np.uint8), fixH=rep("H_fixed", np.uint8))
