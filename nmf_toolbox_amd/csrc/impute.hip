@@ -10,11 +10,11 @@
 // included), a hole never sees V.
 //
 // The kernel is impute_pass.h's, shared with the device entry nmfx_impute_dev (impute_dev.hip); this entry runs its LAYOUT 0 / ImpArgs instantiations.
-// The tile is wcmap_kernel's (wcnmf.hip), copied: 128 x 64 of S per workgroup of four waves, v_mfma_f32_32x32x2_f32 fed transposed so that the epilogue's
-// lanes run along i and every access to V, M and Y is 32 consecutive elements of a column, clamped addresses outside the matrix, the H operand staged once
-// per chunk of 16 k with its T - 1 halo (row stride 17 words), the W double buffer through registers, the rolled two-block epilogue.  float elements of V
-// and M are requested behind the first stage and arrive under the contraction; double elements would be 128 registers there and are loaded in the
-// epilogue, one 32-column half at a time.
+// S is formed on the reconstruction tile that recon_tile.h describes (128 x 64 per workgroup of four waves; staging, halo and LDS layout are described there;
+// impute_pass.h keeps its own text of the contraction and says why), here in its column-major layout: the epilogue's lanes run along i and every access to
+// V, M and Y is 32 consecutive elements of a column, clamped addresses outside the matrix, the rolled two-block epilogue.  float elements of V and M are
+// requested behind the opening stages and arrive under the contraction; double elements would be 128 registers there and are loaded in the epilogue, one
+// 32-column half at a time.
 // Batch: tiles are laid per problem, from the problem's own first column, so a tile never straddles two problems and a problem's tiles are the ones the single
 // call walks; the workgroup finds (b, tile) by bisection in the prefix tile0[0 .. batch] of tiles per problem.  The H halo reads 0 before the problem's first
 // column, never the neighbour's H.  With w_stride != 0 problem b contracts its own W image at b * w_stride.
@@ -37,7 +37,7 @@ void launch_div(hipStream_t st, const ImpArgs &g, bool fill, dim3 grid, size_t l
 template <class ET>
 nmfx_status launch(hipStream_t st, const ImpArgs &g, int div, bool fill, long tiles, long grid_cap) {
     const dim3 grid((unsigned)std::min<long>(tiles, grid_cap));
-    const size_t lds = impute_lds_bytes(g.T);
+    const size_t lds = recon_lds_bytes(g.T);
     switch (div) {
         case IMP_NONE: hipLaunchKernelGGL((impute_kernel<ET, ET, IMP_NONE, true, false, 0, false, ImpArgs>), grid, dim3(256), lds, st, g); break;
         case IMP_EUC: launch_div<ET, IMP_EUC>(st, g, fill, grid, lds); break;
@@ -69,15 +69,15 @@ nmfx_status run_impute(int64_t m, int64_t N, int32_t K, int32_t T, int32_t dtype
             default: set_error("nmfx_impute: fit / held need a divergence (euclidean, kl or is); got %d", divergence); return NMFX_ERR_INVALID;
         }
     }
-    if (T > IMPUTE_MAX_T) { set_error("nmfx_impute: T = %d is not supported (at most %d)", T, IMPUTE_MAX_T); return NMFX_ERR_UNSUPPORTED; }
-    const long grid_cap = impute_grid_cap();
+    if (T > RECON_MAX_T) { set_error("nmfx_impute: T = %d is not supported (at most %d)", T, RECON_MAX_T); return NMFX_ERR_UNSUPPORTED; }
+    const long grid_cap = recon_grid_cap("NMFX_IMPUTE_MAX_GRID");
     DeviceGuard dg_;
     TRY(check_device(device));
     // the work table: a problem's tiles follow from its own shape
-    const long tilesM = (m + IBM - 1) / IBM;
+    const long tilesM = (m + RBM - 1) / RBM;
     std::vector<long> col0(batch + 1), tile0(batch + 1, 0);
     for (int b = 0; b <= batch; ++b) col0[b] = (long)off[b];
-    for (int b = 0; b < batch; ++b) tile0[b + 1] = tile0[b] + tilesM * ((col0[b + 1] - col0[b] + IBN - 1) / IBN);
+    for (int b = 0; b < batch; ++b) tile0[b + 1] = tile0[b] + tilesM * ((col0[b + 1] - col0[b] + RBN - 1) / RBN);
     const long tiles = tile0[batch];
     const size_t es = dsize(dtype), mN = (size_t)m * N, mKT = (size_t)m * K * T * (w_per_problem ? batch : 1), KN = (size_t)K * N;
     const size_t tab = (size_t)(batch + 1) * sizeof(long), parts = score ? (size_t)tiles * sizeof(double) : 0;

@@ -39,9 +39,9 @@ void launch_score(hipStream_t st, const ImpDevArgs &g, bool frames, dim3 grid, s
 }
 template <class MT, int LAYOUT>
 nmfx_status launch_pass(hipStream_t st, const ImpDevArgs &g, int div, bool frames, long grid_cap) {
-    const long tiles = ((g.m + IBM - 1) / IBM) * ((g.n + IBN - 1) / IBN);
+    const long tiles = ((g.m + RBM - 1) / RBM) * ((g.n + RBN - 1) / RBN);
     const dim3 grid((unsigned)std::min<long>(tiles, grid_cap));
-    const size_t lds = impute_lds_bytes(g.T);
+    const size_t lds = recon_lds_bytes(g.T);
     switch (div) {
         case IMP_NONE: hipLaunchKernelGGL((impute_kernel<float, MT, IMP_NONE, true, false, LAYOUT, false, ImpDevArgs>), grid, dim3(256), lds, st, g); break;
         case IMP_EUC: launch_score<MT, LAYOUT, IMP_EUC>(st, g, frames, grid, lds); break;
@@ -54,7 +54,7 @@ nmfx_status launch_pass(hipStream_t st, const ImpDevArgs &g, int div, bool frame
 
 // the float64 partials the scoring pass leaves: 16 bytes per tile, or per (row tile, column)
 bool work_bytes_of(int64_t m, int64_t n, int32_t frames, size_t *bytes) {
-    const int64_t tilesM = (m + IBM - 1) / IBM, tilesN = (n + IBN - 1) / IBN, per_row = frames ? n : tilesN;
+    const int64_t tilesM = (m + RBM - 1) / RBM, tilesN = (n + RBN - 1) / RBN, per_row = frames ? n : tilesN;
     if (tilesM > (INT64_MAX / 16) / per_row) return false;
     *bytes = (size_t)16 * (size_t)tilesM * (size_t)per_row;
     return true;
@@ -105,8 +105,8 @@ extern "C" nmfx_status nmfx_impute_dev(void *stream, int64_t m, int64_t n, int32
             return NMFX_ERR_INVALID;
         }
     }
-    if (T > IMPUTE_MAX_T) { set_error("nmfx_impute_dev: T = %d is not supported (at most %d)", T, IMPUTE_MAX_T); return NMFX_ERR_UNSUPPORTED; }
-    const long grid_cap = impute_grid_cap();
+    if (T > RECON_MAX_T) { set_error("nmfx_impute_dev: T = %d is not supported (at most %d)", T, RECON_MAX_T); return NMFX_ERR_UNSUPPORTED; }
+    const long grid_cap = recon_grid_cap("NMFX_IMPUTE_MAX_GRID");
     DeviceGuard dg_;
     TRY(check_device(device));
     ImpDevArgs g{};
@@ -118,7 +118,7 @@ extern "C" nmfx_status nmfx_impute_dev(void *stream, int64_t m, int64_t n, int32
     if (layout == 0) TRY(m_kind ? (launch_pass<unsigned char, 0>(st, g, div, frames != 0, grid_cap)) : (launch_pass<float, 0>(st, g, div, frames != 0, grid_cap)));
     else TRY(m_kind ? (launch_pass<unsigned char, 1>(st, g, div, frames != 0, grid_cap)) : (launch_pass<float, 1>(st, g, div, frames != 0, grid_cap)));
     if (scores_dev) {
-        const long tilesM = (m + IBM - 1) / IBM, tilesN = (n + IBN - 1) / IBN;
+        const long tilesM = (m + RBM - 1) / RBM, tilesN = (n + RBN - 1) / RBN;
         if (frames) hipLaunchKernelGGL(impute_frames_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g.part, tilesM, (long)n, scores_dev);
         else hipLaunchKernelGGL(impute_totals_kernel, dim3(1), dim3(256), 0, st, g.part, tilesM * tilesN, scores_dev);
         NMFX_HIP(hipGetLastError());

@@ -1,11 +1,12 @@
 // The fused fill-and-score pass of impute / holdout (definition: impute.hip's head) as a template of what differs between its two entries:
 // the host entry nmfx_impute (impute.hip: column-major, packed, a batch of problems found through the device tables col0 / tile0) and the device entry
 // nmfx_impute_dev (impute_dev.hip: one problem whose geometry travels in the kernel arguments, both layouts, leading dimensions, byte masks, per-column scores).
-//   LAYOUT 0, column-major: element (i, j) of V at V[i + ldv*j] (M, Y alike).  The MFMA is fed transposed (A = the H stage, B = W), so a lane of the
-//       accumulator holds one row i and 16 columns: every access to V, M and Y is 32 consecutive elements of a column.
-//   LAYOUT 1, row-major: element (i, j) at V[i*ldv + j].  The operands change places (A = W, B = the H stage): a lane holds one column j and 16 rows, every
-//       access is 32 consecutive elements of a row.  The LDS reads are the same addresses by the same lanes in both layouts -- only the operand slot they
-//       feed differs -- and a*b + c is b*a + c, so every product and every order of accumulation is the same: the filled entries are the same bits.
+// The tile is recon_tile.h's (its constants, LDS layout, limit on T and the two layouts of the accumulator are taken from there), but THIS KERNEL KEEPS ITS OWN
+// TEXT OF THE CONTRACTION: on recon_contract its row-major and per-column instantiations came out 3 to 4 % slower per launch (the products and their order
+// the same, the results the same bits; another instruction order and register assignment: profiles/refactor_recon_tile.md).  A change to recon_contract's
+// staging has to be made here too.
+//   LAYOUT 0, column-major: element (i, j) of V at V[i + ldv*j] (M, Y alike); a lane holds one row i and 16 columns.
+//   LAYOUT 1, row-major: element (i, j) at V[i*ldv + j]; a lane holds one column j and 16 rows.  S, and so every filled entry, is the same bits in both.
 //   MT: the element of M -- ET (weights: on = M > 0) or unsigned char (a byte mask: on = M != 0, weight 1), read with the access pattern of V.
 //   FRAMES: besides (instead of) the one pair of float64 partials per tile, one pair per (row tile, column): part[(tile row * n + j) * 2 + {fit, held}].
 // Sums: no atomics.  Totals: each TILE leaves one pair of partials (block_sum256 over the lanes' sums: a fixed order).  FRAMES: the 128 rows of a tile's
@@ -22,14 +23,12 @@
 #include "api_common.h"
 #include "dev_reduce.h"
 #include "gemm_common.h"
+#include "recon_tile.h"
 
 namespace nmfx {
 namespace {
 
 enum ImpDiv { IMP_NONE = 0, IMP_EUC = 1, IMP_KL = 2, IMP_IS = 3 };
-
-constexpr int IBM = 128, IBN = 64, IBK = 16, ILDH = IBK + 1;
-constexpr int IMPUTE_MAX_GRID = 8192, IMPUTE_MAX_T = 64;   // (the kernel's opening H fill covers 128 stage columns: 64 + T - 1 <= 127)
 
 struct ImpArgs {            // nmfx_impute: packed column-major, `batch` problems side by side
     const float *W, *H;     // fp32 images: W[i + m*(t*K + k)] (+ b * w_stride), H[k + K*j], j over all N columns
@@ -60,26 +59,6 @@ struct ImpDevArgs {         // nmfx_impute_dev: one m x n problem, views with le
     __device__ long ldy() const { return ldy_; }
 };
 
-inline size_t impute_lds_bytes(int T) { return (size_t)2 * (IBN + T - 1) * ILDH * sizeof(float); }
-
-inline long impute_grid_cap() {   // NMFX_IMPUTE_MAX_GRID, read per call: lowers the workgroup count (how a small matrix makes a workgroup take several tiles)
-    long grid_cap = IMPUTE_MAX_GRID;
-    if (const char *c = getenv("NMFX_IMPUTE_MAX_GRID")) {
-        const long v = atol(c);
-        if (v >= 1 && v < grid_cap) grid_cap = v;
-    }
-    return grid_cap;
-}
-
-template <class MT> struct ImpWeight {   // a weight: observed where it is positive
-    static __device__ __forceinline__ bool on(MT w) { return w > (MT)0; }
-    static __device__ __forceinline__ double times(MT w, double c) { return (double)w * c; }
-};
-template <> struct ImpWeight<unsigned char> {   // a byte of a bool / uint8 mask: observed where it is non-zero, weight 1
-    static __device__ __forceinline__ bool on(unsigned char w) { return w != 0; }
-    static __device__ __forceinline__ double times(unsigned char, double c) { return c; }
-};
-
 // The halving exchange of the head behind its first step: a[k] holds the lane's sums after the xor-16 step.  a[0] of lane l <- the sum over the 16 lanes
 // l ^ {0 .. 15} of their a[((l & 31) >> 1) & 7].  Every lane calls it.
 __device__ __forceinline__ void lanes_sum8(double (&a)[8]) {
@@ -104,19 +83,19 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
     constexpr bool PREFETCH = sizeof(ET) == 4;
     typedef ET e16 __attribute__((ext_vector_type(16)));
     typedef MT m16t __attribute__((ext_vector_type(16)));
-    __shared__ float Ws[2][IBK * IBM];
-    extern __shared__ float Hs[];                    // [2][(IBN + T - 1) * ILDH]
+    __shared__ float Ws[2][RBK * RBM];
+    extern __shared__ float Hs[];                    // recon_lds_bytes(T)
     __shared__ double sh[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-    const long tilesM = (g.m + IBM - 1) / IBM;
+    const long tilesM = (g.m + RBM - 1) / RBM;
     long tilesN = 0, tiles;
     if constexpr (ARGS::TABLES) tiles = g.tile0[g.batch];
-    else { tilesN = (g.n + IBN - 1) / IBN; tiles = tilesM * tilesN; }
-    const int K = g.K, T = g.T, nk = (K + IBK - 1) / IBK;
-    const int hcols = IBN + T - 1, hstage = hcols * ILDH;
+    else { tilesN = (g.n + RBN - 1) / RBN; tiles = tilesM * tilesN; }
+    const int K = g.K, T = g.T, nk = (K + RBK - 1) / RBK;
+    const int hcols = RBN + T - 1, hstage = hcols * RLDH;
     // loaders: consecutive threads along the operand's contiguous dimension (W: i, H: k)
-    const int w_r = tid & (IBM - 1), w_k = tid >> 7;      // + 2 u, u < 8
-    const int h_k = tid & (IBK - 1), h_c = tid >> 4;      // + 16 u
+    const int w_r = tid & (RBM - 1), w_k = tid >> 7;      // + 2 u, u < 8
+    const int h_k = tid & (RBK - 1), h_c = tid >> 4;      // + 16 u
     for (long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
         long c0, nb, i0, j0;
         const float *Wb, *Hb;
@@ -128,13 +107,13 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
             }
             c0 = g.col0[b]; nb = g.col0[b + 1] - c0;
             const long tp = tl - g.tile0[b];
-            i0 = (tp % tilesM) * IBM; j0 = (tp / tilesM) * IBN;      // j0: a column of the PROBLEM
+            i0 = (tp % tilesM) * RBM; j0 = (tp / tilesM) * RBN;      // j0: a column of the PROBLEM
             Wb = g.W + (long)b * g.w_stride; Hb = g.H + (long)K * c0;
         } else {
             // consecutive tiles -- the ones in flight together -- are neighbours along the contiguous dimension of V, M and Y
             c0 = 0; nb = g.n; Wb = g.W; Hb = g.H;
-            if constexpr (LAYOUT == 0) { i0 = (tl % tilesM) * IBM; j0 = (tl / tilesM) * IBN; }
-            else { i0 = (tl / tilesN) * IBM; j0 = (tl % tilesN) * IBN; }
+            if constexpr (LAYOUT == 0) { i0 = (tl % tilesM) * RBM; j0 = (tl / tilesM) * RBN; }
+            else { i0 = (tl / tilesN) * RBM; j0 = (tl % tilesN) * RBN; }
         }
         const long jh = j0 - (T - 1);                                 // the problem's column of stage column 0
         const long ldv = g.ldv(), ldm = g.ldm();
@@ -151,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
         };
         auto wstore = [&](int buf) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) Ws[buf][(w_k + 2 * u) * IBM + w_r] = rw[u];
+            for (int u = 0; u < 8; ++u) Ws[buf][(w_k + 2 * u) * RBM + w_r] = rw[u];
         };
         auto hval = [&](int k0, int c) {   // stage column c of the chunk at k0: 0 before the problem's first column and past its last
             const long j = jh + c;
@@ -170,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int c = 64 * q + h_c + 16 * u;
-                if (c < hcols) Hs[buf * hstage + c * ILDH + h_k] = rh[u];
+                if (c < hcols) Hs[buf * hstage + c * RLDH + h_k] = rh[u];
             }
         };
         f32x16 acc[2];
@@ -191,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int c = h_c + 16 * u;
-            if (c < hcols) Hs[c * ILDH + h_k] = ph[u];
+            if (c < hcols) Hs[c * RLDH + h_k] = ph[u];
         }
         // With r(e) = (e & 3) + 8 (e >> 2) + 4 (lane >> 5), acc[y][e] is
         //   LAYOUT 0: column (lane & 31) -> i, row r(e) -> j:  i = i0 + 32 wave + (lane & 31), j = j0 + 32 y + r(e)
@@ -233,16 +212,16 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
             const int buf = s & 1, hbuf = kc & 1;
             const bool last_t = t + 1 == T, more = s + 1 < ns, hnext = kc + 1 < nk && 64 * t < hcols;
             const int tn = last_t ? 0 : t + 1, kn = last_t ? kc + 1 : kc;
-            if (more) wload(kn * IBK, tn);
-            if (hnext) hload((kc + 1) * IBK, t);
-            const float *a = Ws[buf], *bq = Hs + hbuf * hstage + ((T - 1) - t) * ILDH;
+            if (more) wload(kn * RBK, tn);
+            if (hnext) hload((kc + 1) * RBK, t);
+            const float *a = Ws[buf], *bq = Hs + hbuf * hstage + ((T - 1) - t) * RLDH;
 #pragma unroll
-            for (int kk = 0; kk < IBK / 2; ++kk) {
+            for (int kk = 0; kk < RBK / 2; ++kk) {
                 const int k = 2 * kk + lh;
-                const float wf = a[k * IBM + 32 * wv + l31];
+                const float wf = a[k * RBM + 32 * wv + l31];
 #pragma unroll
                 for (int y = 0; y < 2; ++y) {
-                    const float hf = bq[(32 * y + l31) * ILDH + k];
+                    const float hf = bq[(32 * y + l31) * RLDH + k];
                     if constexpr (LAYOUT == 0) acc[y] = __builtin_amdgcn_mfma_f32_32x32x2f32(hf, wf, acc[y], 0, 0, 0);   // D(row = j, col = i)
                     else acc[y] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf, hf, acc[y], 0, 0, 0);                         // D(row = i, col = j)
                 }
@@ -254,9 +233,9 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
         }
         // The rolled two-block epilogue of wmap_kernel: the second accumulator block moves into the first one's place
         double pfit = 0.0, pheld = 0.0;
-        double *fs = nullptr;                   // FRAMES: [4 waves][IBN columns][2] in LDS
+        double *fs = nullptr;                   // FRAMES: [4 waves][RBN columns][2] in LDS
         if constexpr (FRAMES) {
-            __shared__ double frame_sums[4 * IBN * 2];
+            __shared__ double frame_sums[4 * RBN * 2];
             fs = frame_sums;
         }
 #pragma unroll 1
@@ -278,7 +257,7 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
                 const float s = s16[e];
                 const ET v = v16[e];
                 const MT w = m16[e];
-                const bool inside = r < g.m && j < nb, on = ImpWeight<MT>::on(w) && inside;
+                const bool inside = r < g.m && j < nb, on = Weight<MT>::on(w) && inside;
                 if constexpr (FILL) {
                     const long ldy = g.ldy();      // (c0 + j: the column of the packed batch; c0 = 0 where there is no batch)
                     if (inside) static_cast<ET *>(g.Y)[LAYOUT == 0 ? r + ldy * (c0 + j) : r * ldy + j] = on ? v : (ET)s;
@@ -289,7 +268,7 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
                     if constexpr (DIV == IMP_EUC) { const double d = vd - sd; c = 0.5 * (d * d); }
                     else if constexpr (DIV == IMP_KL) c = (vd * log(vd / sd) - vd) + sd;
                     else c = (log(sd / vd) + vd / sd) - 1.0;
-                    const double tf = on ? ImpWeight<MT>::times(w, c) : 0.0, th = (!on && inside) ? c : 0.0;
+                    const double tf = on ? Weight<MT>::times(w, c) : 0.0, th = (!on && inside) ? c : 0.0;
                     if constexpr (FRAMES && LAYOUT == 0) {
                         if ((e & 1) == 0) { ef = tf; eh = th; }      // (waits for its odd neighbour)
                         else {                                       // step xor 16: the upper lanes keep the odd column, the lower ones the even one
@@ -305,8 +284,8 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
                 pfit += __shfl_xor(pfit, 32);
                 pheld += __shfl_xor(pheld, 32);
                 if (lh == 0) {
-                    fs[(wv * IBN + 32 * y + l31) * 2] = pfit;
-                    fs[(wv * IBN + 32 * y + l31) * 2 + 1] = pheld;
+                    fs[(wv * RBN + 32 * y + l31) * 2] = pfit;
+                    fs[(wv * RBN + 32 * y + l31) * 2 + 1] = pheld;
                 }
             }
             if constexpr (FRAMES && LAYOUT == 0) {       // a column's 32 rows of this wave sit in the 32 lanes of a half
@@ -314,19 +293,19 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
                 lanes_sum8(ch);
                 if ((l31 & 1) == 0) {
                     const int e = 2 * ((l31 >> 1) & 7) + (l31 >> 4), c = 32 * y + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                    fs[(wv * IBN + c) * 2] = cf[0];
-                    fs[(wv * IBN + c) * 2 + 1] = ch[0];
+                    fs[(wv * RBN + c) * 2] = cf[0];
+                    fs[(wv * RBN + c) * 2 + 1] = ch[0];
                 }
             }
         }
         if constexpr (FRAMES) {          // the four waves (32 rows each) in index order; one pair per (row tile, column)
             __syncthreads();
-            if (tid < 2 * IBN) {
+            if (tid < 2 * RBN) {
                 const int c = tid >> 1, q = tid & 1;
-                const double sum = ((fs[c * 2 + q] + fs[(IBN + c) * 2 + q]) + fs[(2 * IBN + c) * 2 + q]) + fs[(3 * IBN + c) * 2 + q];
+                const double sum = ((fs[c * 2 + q] + fs[(RBN + c) * 2 + q]) + fs[(2 * RBN + c) * 2 + q]) + fs[(3 * RBN + c) * 2 + q];
                 const long j = j0 + c;
                 if constexpr (!ARGS::TABLES)
-                    if (j < nb) g.part[((i0 / IBM) * g.n + j) * 2 + q] = sum;
+                    if (j < nb) g.part[((i0 / RBM) * g.n + j) * 2 + q] = sum;
             }
             __syncthreads();             // (fs is free for the next tile)
         } else if constexpr (SCORE) {    // per TILE, not per workgroup: the partials do not know the grid
@@ -335,7 +314,7 @@ __global__ __launch_bounds__(256, 2) void impute_kernel(const ARGS g) {
             if (tid == 0) {
                 if constexpr (ARGS::TABLES) { g.fit[tl] = pfit; g.held[tl] = pheld; }
                 else {
-                    const long tile = i0 / IBM + tilesM * (j0 / IBN);
+                    const long tile = i0 / RBM + tilesM * (j0 / RBN);
                     g.part[2 * tile] = pfit; g.part[2 * tile + 1] = pheld;
                 }
             }

@@ -8,11 +8,9 @@
 // r_i is formed first, so the masks do not change when W (or H) is scaled by a power of two, and q cannot overflow.  The masks are fp32 whatever X is:
 // a float64 X only has mask .* X done in double.  X never enters a mask: what is not finite in X reaches that element of every Y_i and nothing else.
 //
-// The tile is wcmap_kernel's (wcnmf.hip): 128 x 64 of S per workgroup of four waves, v_mfma_f32_32x32x2_f32 fed transposed so that the epilogue's lanes run
-// along i and every store is 32 consecutive elements of a column, clamped addresses outside the matrix, the H operand staged once per chunk of 16 k with its
-// halo (stage columns j0 - (T - 1) .. j0 + 63, those before column 0 zero-filled in LDS; row stride 17 words, conflict-free at any column offset -- reasoning
-// from the bank layout, no counter was read), W stages double-buffered through registers, a k tail zero-filled in LDS.  Here the contraction is a function
-// of a k RANGE (contract: kb .. ke - 1), because every source is contracted on its own chunks into its own accumulators.
+// Every S_i is formed by the reconstruction tile of recon_tile.h (128 x 64 per workgroup of four waves; staging, halo and LDS layout are described there),
+// here in its column-major layout: the epilogue's lanes run along i and every store is 32 consecutive elements of a column, clamped addresses outside the
+// matrix.  The contraction is called on a k RANGE (kb .. ke - 1), because every source is contracted on its own chunks into its own accumulators.
 //   register form (I <= 4, NS = 2 | 4 accumulator pairs): one sweep, source by source; the epilogue forms S = ((S_0 + S_1) + S_2) + S_3, r, q, their sum and
 //       the I products.  An accumulator pair past I stays zero: it adds +0 and changes no bit.
 //   sweep form (any I; NS = 0): three sweeps with three live accumulator pairs: S over all K; D = sum_j (S_j/S)^p source by source; S_i again and the
@@ -29,9 +27,9 @@ namespace {
 
 template <class ET, int PW, bool MASKS>
 nmfx_status launch_form(hipStream_t st, const SMArgs &g, bool sweep, long grid_cap) {
-    const long tiles = ((g.m + SBM - 1) / SBM) * ((g.n + SBN - 1) / SBN);
+    const long tiles = ((g.m + RBM - 1) / RBM) * ((g.n + RBN - 1) / RBN);
     const dim3 grid((unsigned)std::min<long>(tiles, grid_cap)), block(256);
-    const size_t lds = softmask_lds_bytes(g.T);
+    const size_t lds = recon_lds_bytes(g.T);
     if (sweep) hipLaunchKernelGGL((softmask_kernel<ET, PW, MASKS, 0, 0, SMArgs>), grid, block, lds, st, g);
     else if (g.I <= 2) hipLaunchKernelGGL((softmask_kernel<ET, PW, MASKS, 2, 0, SMArgs>), grid, block, lds, st, g);
     else hipLaunchKernelGGL((softmask_kernel<ET, PW, MASKS, 4, 0, SMArgs>), grid, block, lds, st, g);
@@ -58,7 +56,7 @@ nmfx_status run_softmask(int64_t m, int64_t n, int32_t I, const int32_t *K_s, in
         if ((long)koff[s] + K_s[s] > (1L << 24)) { set_error("nmfx_softmask: sum(K_s) is too large"); return NMFX_ERR_INVALID; }
         koff[s + 1] = koff[s] + K_s[s];
     }
-    if (T > SOFTMASK_MAX_T) { set_error("nmfx_softmask: T = %d is not supported (at most %d)", T, SOFTMASK_MAX_T); return NMFX_ERR_UNSUPPORTED; }
+    if (T > RECON_MAX_T) { set_error("nmfx_softmask: T = %d is not supported (at most %d)", T, RECON_MAX_T); return NMFX_ERR_UNSUPPORTED; }
     bool sweep;
     long grid_cap;
     TRY(softmask_env("nmfx_softmask", I, &sweep, &grid_cap));

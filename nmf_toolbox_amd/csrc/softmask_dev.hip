@@ -11,9 +11,9 @@ namespace {
 
 template <class ET, int PW, bool MASKS, int LAYOUT>
 nmfx_status launch_form(hipStream_t st, const SMDevArgs &g, bool sweep, long grid_cap) {
-    const long tiles = ((g.m + SBM - 1) / SBM) * ((g.n + SBN - 1) / SBN);
+    const long tiles = ((g.m + RBM - 1) / RBM) * ((g.n + RBN - 1) / RBN);
     const dim3 grid((unsigned)std::min<long>(tiles, grid_cap)), block(256);
-    const size_t lds = softmask_lds_bytes(g.T);
+    const size_t lds = recon_lds_bytes(g.T);
     if (sweep) hipLaunchKernelGGL((softmask_kernel<ET, PW, MASKS, 0, LAYOUT, SMDevArgs>), grid, block, lds, st, g);
     else if (g.I <= 2) hipLaunchKernelGGL((softmask_kernel<ET, PW, MASKS, 2, LAYOUT, SMDevArgs>), grid, block, lds, st, g);
     else hipLaunchKernelGGL((softmask_kernel<ET, PW, MASKS, 4, LAYOUT, SMDevArgs>), grid, block, lds, st, g);
@@ -56,7 +56,7 @@ extern "C" nmfx_status nmfx_softmask_dev(void *stream, int64_t m, int64_t n, int
         set_error("nmfx_softmask_dev: y_slab = %lld is too small for one output (ldy * %lld + %lld elements)", (long long)y_slab, (long long)(other - 1), (long long)lead);
         return NMFX_ERR_INVALID;
     }
-    if (T > SOFTMASK_MAX_T) { set_error("nmfx_softmask_dev: T = %d is not supported (at most %d)", T, SOFTMASK_MAX_T); return NMFX_ERR_UNSUPPORTED; }
+    if (T > RECON_MAX_T) { set_error("nmfx_softmask_dev: T = %d is not supported (at most %d)", T, RECON_MAX_T); return NMFX_ERR_UNSUPPORTED; }
     bool sweep;
     long grid_cap;
     TRY(softmask_env("nmfx_softmask_dev", I, &sweep, &grid_cap));

@@ -1,22 +1,18 @@
 // The fused softmask pass (definition: softmask.hip's head) as a template of the storage layout of X and Y, shared by the host entry
 // nmfx_softmask (softmask.hip: LAYOUT 0, packed) and the device entry nmfx_softmask_dev (softmask_dev.hip: both layouts, with leading dimensions).
-//   LAYOUT 0, column-major: element (i, j) of X at X[i + ldx*j], of Y_s at Y[s*slab + i + ldy*j].  The MFMA is fed transposed (A = the H stage, B = W), so
-//       a lane of the accumulator holds one row i and 16 columns: every load of X and store of Y is 32 consecutive elements of a column.
-//   LAYOUT 1, row-major: element (i, j) at X[i*ldx + j], Y[s*slab + i*ldy + j].  The operands change places (A = W, B = the H stage): a lane holds one column
-//       j and 16 rows, every access is 32 consecutive elements of a row.  The LDS reads are the same addresses by the same lanes in both layouts -- only the
-//       operand slot they feed differs -- and a*b + c is b*a + c, so every product and every order of accumulation is the same: the layouts give the same bits.
+// The contraction and the two layouts of its accumulator are recon_tile.h's; what is here is the register and sweep forms of the mask epilogue.
+//   LAYOUT 0, column-major: element (i, j) of X at X[i + ldx*j], of Y_s at Y[s*slab + i + ldy*j]; a lane holds one row i and 16 columns.
+//   LAYOUT 1, row-major: element (i, j) at X[i*ldx + j], Y[s*slab + i*ldy + j]; a lane holds one column j and 16 rows.  The layouts give the same bits.
 // ARGS supplies the sizes: SMArgs (packed: ldx = ldy = m, slab = m*n, no further kernel arguments) or SMDevArgs.
 #pragma once
 #include <type_traits>
 
 #include "api_common.h"
 #include "gemm_common.h"
+#include "recon_tile.h"
 
 namespace nmfx {
 namespace {
-
-constexpr int SBM = 128, SBN = 64, SBK = 16, SLDH = SBK + 1;
-constexpr int SOFTMASK_MAX_GRID = 8192, SOFTMASK_MAX_T = 64;   // (the opening H fill covers 128 stage columns: 64 + T - 1 <= 127)
 
 struct SMArgs {
     const float *W, *H;     // fp32 images: W[i + m*(t*K + k)], H[k + K*j]
@@ -44,8 +40,6 @@ struct SMDevArgs {          // SMArgs + the strides of a view: leading dimension
     __device__ long slab() const { return slab_; }
 };
 
-inline size_t softmask_lds_bytes(int T) { return (size_t)2 * (SBN + T - 1) * SLDH * sizeof(float); }
-
 // the two switches both entries read per call: NMFX_SOFTMASK_FORM = register | sweep (default: register up to 4 sources) and NMFX_SOFTMASK_MAX_GRID
 inline nmfx_status softmask_env(const char *fn, int I, bool *sweep, long *grid_cap) {
     *sweep = I > 4;
@@ -55,11 +49,7 @@ inline nmfx_status softmask_env(const char *fn, int I, bool *sweep, long *grid_c
             if (I > 4) { set_error("%s: NMFX_SOFTMASK_FORM=register needs at most 4 sources", fn); return NMFX_ERR_INVALID; }
         } else if (*f) { set_error("%s: NMFX_SOFTMASK_FORM must be 'register' or 'sweep'", fn); return NMFX_ERR_INVALID; }
     }
-    *grid_cap = SOFTMASK_MAX_GRID;
-    if (const char *c = getenv("NMFX_SOFTMASK_MAX_GRID")) {
-        const long v = atol(c);
-        if (v >= 1 && v < *grid_cap) *grid_cap = v;
-    }
+    *grid_cap = recon_grid_cap("NMFX_SOFTMASK_MAX_GRID");
     return NMFX_OK;
 }
 
@@ -79,97 +69,6 @@ template <int PW> __device__ __forceinline__ float mask_pow(float r, float p) {
     else return exp2f(p * log2f(r));
 }
 
-// acc += sum_t W_t(i0 .. i0 + 127, kb .. ke - 1) * rshift_t(H)(kb .. ke - 1, j0 .. j0 + 63).  Every thread of the workgroup calls it; the LDS is free on
-// entry (the loop below ends behind a barrier) and on return.  With r(e) = (e & 3) + 8 (e >> 2) + 4 (lane >> 5), acc[y][e] is
-//   LAYOUT 0: i = i0 + 32 wave + (lane & 31), j = j0 + 32 y + r(e)          LAYOUT 1: i = i0 + 32 wave + r(e), j = j0 + 32 y + (lane & 31)
-template <int LAYOUT, class ARGS>
-__device__ __forceinline__ void contract(const ARGS &g, float *Ws, float *Hs, long i0, long j0, int kb, int ke, f32x16 &acc0, f32x16 &acc1) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-    const int K = g.K, T = g.T, nk = (ke - kb + SBK - 1) / SBK;
-    const int hcols = SBN + T - 1, hstage = hcols * SLDH;
-    const long jh = j0 - (T - 1);                         // the global column of stage column 0
-    const int w_r = tid & (SBM - 1), w_k = tid >> 7;      // + 2 u, u < 8
-    const int h_k = tid & (SBK - 1), h_c = tid >> 4;      // + 16 u
-    float rw[8], rh[4], ph[8];
-    auto wload = [&](int k0, int t) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const long i = i0 + w_r;
-            const int k = k0 + w_k + 2 * u;
-            rw[u] = (i < g.m && k < ke) ? g.W[i + g.m * ((long)t * K + k)] : 0.0f;
-        }
-    };
-    auto wstore = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) Ws[buf * (SBK * SBM) + (w_k + 2 * u) * SBM + w_r] = rw[u];
-    };
-    auto hval = [&](int k0, int c) {   // stage column c of the chunk at k0
-        const long j = jh + c;
-        const int k = k0 + h_k;
-        return (j >= 0 && j < g.n && k < ke) ? g.H[k + (long)K * j] : 0.0f;
-    };
-    auto hload = [&](int k0, int q) {  // slice q of a chunk's H stage: stage columns 64 q + h_c + 16 u, u < 4
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = 64 * q + h_c + 16 * u;
-            rh[u] = c < hcols ? hval(k0, c) : 0.0f;
-        }
-    };
-    auto hstore = [&](int buf, int q) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = 64 * q + h_c + 16 * u;
-            if (c < hcols) Hs[buf * hstage + c * SLDH + h_k] = rh[u];
-        }
-    };
-    // the first stages: W_0 of chunk 0 and the whole H stage of chunk 0, halo included (8 x 16 columns >= 64 + T - 1 for T <= 64), every load before the first store
-    wload(kb, 0);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int c = h_c + 16 * u;
-        ph[u] = c < hcols ? hval(kb, c) : 0.0f;
-    }
-    wstore(0);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int c = h_c + 16 * u;
-        if (c < hcols) Hs[c * SLDH + h_k] = ph[u];
-    }
-    __syncthreads();
-    int t = 0, kc = 0;
-    for (int s = 0, ns = nk * T; s < ns; ++s) {
-        const int buf = s & 1, hbuf = kc & 1;
-        const bool last_t = t + 1 == T, more = s + 1 < ns, hnext = kc + 1 < nk && 64 * t < hcols;
-        const int tn = last_t ? 0 : t + 1, kn = last_t ? kc + 1 : kc;
-        if (more) wload(kb + kn * SBK, tn);
-        if (hnext) hload(kb + (kc + 1) * SBK, t);
-        const float *a = Ws + buf * (SBK * SBM), *b = Hs + hbuf * hstage + ((T - 1) - t) * SLDH;
-#pragma unroll
-        for (int kk = 0; kk < SBK / 2; ++kk) {
-            const int k = 2 * kk + lh;
-            const float wf = a[k * SBM + 32 * wv + l31];
-            if constexpr (LAYOUT == 0) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(b[l31 * SLDH + k], wf, acc0, 0, 0, 0);          // D(row = j, col = i)
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b[(32 + l31) * SLDH + k], wf, acc1, 0, 0, 0);
-            } else {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(wf, b[l31 * SLDH + k], acc0, 0, 0, 0);          // D(row = i, col = j)
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(wf, b[(32 + l31) * SLDH + k], acc1, 0, 0, 0);
-            }
-        }
-        if (more) wstore(buf ^ 1);          // (the other buffer: last read one trip ago, behind the barrier below)
-        if (hnext) hstore(hbuf ^ 1, t);     // (the other H buffer: last read in the chunk before this one)
-        __syncthreads();
-        t = tn; kc = kn;
-    }
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) z[e] = 0.0f;
-    return z;
-}
-
 // ET: the element of X and of the estimates; MASKS: store the masks (as ET's real type; X is not read); PW: see mask_pow; NS: 0 = sweep form, else the
 // accumulator pairs of the register form (g.I <= NS); LAYOUT and ARGS: see the head
 template <class ET, int PW, bool MASKS, int NS, int LAYOUT, class ARGS>
@@ -177,10 +76,10 @@ __global__ __launch_bounds__(256, 2) void softmask_kernel(const ARGS g) {
     typedef typename Elem<ET>::real RT;
     typedef typename std::conditional<MASKS, RT, ET>::type OT;
     constexpr int XC = (sizeof(ET) == 16 ? 8 : 16) / (NS == 2 ? 1 : 2);   // elements per epilogue step (halved where four accumulator pairs, or S and D, are live)
-    __shared__ float Ws[2 * SBK * SBM];
-    extern __shared__ float Hs[];                    // [2][(SBN + T - 1) * SLDH]
+    __shared__ float Ws[2 * RBK * RBM];
+    extern __shared__ float Hs[];                    // recon_lds_bytes(T)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-    const long tilesM = (g.m + SBM - 1) / SBM, tilesN = (g.n + SBN - 1) / SBN, tiles = tilesM * tilesN, mn = g.slab();
+    const long tilesM = (g.m + RBM - 1) / RBM, tilesN = (g.n + RBN - 1) / RBN, tiles = tilesM * tilesN, mn = g.slab();
     const int I = g.I;
     const float even = 1.0f / (float)I;
     const ET *X = static_cast<const ET *>(g.X);
@@ -188,8 +87,8 @@ __global__ __launch_bounds__(256, 2) void softmask_kernel(const ARGS g) {
     for (long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
         // consecutive tiles -- the ones in flight together -- are neighbours along the contiguous dimension of X and Y
         long i0, j0;
-        if constexpr (LAYOUT == 0) { i0 = (tl % tilesM) * SBM; j0 = (tl / tilesM) * SBN; }
-        else { i0 = (tl / tilesN) * SBM; j0 = (tl % tilesN) * SBN; }
+        if constexpr (LAYOUT == 0) { i0 = (tl % tilesM) * RBM; j0 = (tl / tilesM) * RBN; }
+        else { i0 = (tl / tilesN) * RBM; j0 = (tl % tilesN) * RBN; }
         // LAYOUT 0: the lane's row i and its first column jl; col(y, e) is the column of accumulator element (y, e)
         // LAYOUT 1: the lane's first row i and its column jl in the tile's first half; col(y, e) is the element's (row, column)
         const long i = i0 + 32 * wv + (LAYOUT == 0 ? l31 : 4 * lh);
@@ -237,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void softmask_kernel(const ARGS g) {
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 acc[s][0] = zero16(); acc[s][1] = zero16();
-                if (s < I) contract<LAYOUT>(g, Ws, Hs, i0, j0, g.koff[s], g.koff[s + 1], acc[s][0], acc[s][1]);
+                if (s < I) recon_contract<LAYOUT>(g.W, g.H, g.m, g.n, g.K, g.T, g.koff[s], g.koff[s + 1], i0, j0, Ws, Hs, acc[s][0], acc[s][1]);
             }
 #pragma unroll
             for (int y = 0; y < 2; ++y)
@@ -272,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void softmask_kernel(const ARGS g) {
                 const int s = job == 0 ? 0 : (job <= I ? job - 1 : job - 1 - I);
                 const int kb = job == 0 ? 0 : g.koff[s], ke = job == 0 ? g.K : g.koff[s + 1];
                 f32x16 a[2] = {zero16(), zero16()};
-                contract<LAYOUT>(g, Ws, Hs, i0, j0, kb, ke, a[0], a[1]);
+                recon_contract<LAYOUT>(g.W, g.H, g.m, g.n, g.K, g.T, kb, ke, i0, j0, Ws, Hs, a[0], a[1]);
                 // (the element addresses below do not depend on the job: left alone the compiler computes all 32 of them once per tile and keeps 64 registers
                 // alive across the contractions, which is what spills; opaque copies of the lane's row and first column tie them to this trip)
                 asm volatile("" : "+v"(ic), "+v"(jl));

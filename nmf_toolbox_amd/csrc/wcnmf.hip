@@ -22,29 +22,22 @@
 // P_all = B*H_stack' (m x KT, VIEW_HSTACK_RC) and Q_A = W_flat'*A, Q_B = W_flat'*B (KT x n); the H update (wc_h_update_kernel) does the shift-sum of both,
 // the kl tail and the float64 update in one launch.
 //
-// The convolutive weighted map pass (wcmap_kernel) is wmap_kernel's tile -- 128 x 64 of S per workgroup of four waves, v_mfma_f32_32x32x2_f32 fed transposed
-// so that the epilogue's lanes run along i, V and M requested behind the first stage, clamped addresses outside the matrix, the rolled two-block epilogue,
-// float64 cost terms, one float64 partial per workgroup -- with the contraction over (k-chunk, t).  The H operand is staged ONCE per chunk of 16 k, with its
-// halo: the stage holds H(k0 .. k0 + 15, j0 - (T - 1) .. j0 + 63), 64 + T - 1 columns (those before column 0 zero-filled in LDS), and for each t the stage of
-// W_t (16 k x 128 rows) is contracted against the same H stage read at column offset (T - 1) - t.  H passes through LDS once per chunk instead of T times;
-// nothing is stacked or padded in HBM; a K tail is zero-filled in LDS.  Double buffering: the next W stage is in flight in registers while this one is
-// contracted; the NEXT chunk's H stage is requested in slices of 4 elements per thread and t-stage (4*256*T >= 16*(63 + T) for every T >= 1) and written to
-// the other H buffer, which nobody reads before the chunk changes.
-// LDS: W stages [2][16][128] floats, static (a half wave reads 32 consecutive floats); H stages [2][64 + T - 1][17] floats, dynamic (at most 17272 bytes at
-// T = 64).  The H row stride is 17 words: ds_read_b32 banks are word address mod 32 per 32-lane half, a half reads 32 consecutive stage columns at one k,
-// 17*c mod 32 is a permutation of the banks for any column offset, so no read conflicts whatever (T - 1) - t is.  (Reasoning from the bank layout; no counter
-// was read.)
+// The convolutive weighted map pass (wcmap_kernel) forms S on the reconstruction tile that recon_tile.h describes -- 128 x 64 of S per workgroup, the
+// contraction over (k-chunk, t) with the H stage and its halo loaded once per chunk; the staging, the LDS layout and its bank argument are described there,
+// and its constants, LDS size and limit on T are the header's -- in the column-major layout, so that the epilogue's lanes run along i; V and M requested
+// behind the opening stages, clamped addresses outside the matrix; the rolled two-block element map of wmap_kernel (wnmf_pass.h), the A / B stores, float64
+// cost terms, one float64 partial per workgroup.  THE KERNEL KEEPS ITS OWN TEXT OF THE CONTRACTION: on recon_contract (with a callable behind the opening
+// stages, or split into open / run halves) the results were the same bits, but three to four of its nine instantiations were 1 to 5 % slower per launch,
+// outside the parent's own spread (profiles/refactor_recon_tile.md).  A change to recon_contract's staging has to be made here too.
 #include "api_common.h"
 #include "dev_reduce.h"
 #include "gemm_common.h"
+#include "recon_tile.h"
 
 namespace nmfx {
 namespace {
 
-enum WCMap { WC_EUC = 0, WC_KL = 1, WC_IS = 2 };
-
-constexpr int CBM = 128, CBN = 64, CBK = 16, CLDH = CBK + 1;
-constexpr int WCMAP_MAX_GRID = 8192, WCNMF_MAX_T = 64;   // (the kernel's opening H fill covers 128 stage columns: 64 + T - 1 <= 127)
+enum WCMap { WC_EUC = NMFX_DIV_EUCLIDEAN, WC_KL = NMFX_DIV_KL, WC_IS = NMFX_DIV_IS };   // (div_term's numbering)
 
 struct WCMapArgs {
     const float *W, *H;     // fp32 images: W[i + m*(t*K + k)], H[k + K*j]
@@ -55,24 +48,22 @@ struct WCMapArgs {
     double *partials;       // [gridDim.x] weighted data-fit partials of a cost pass
 };
 
-inline size_t wcmap_lds_bytes(int T) { return (size_t)2 * (CBN + T - 1) * CLDH * sizeof(float); }
-
 template <int MAP, bool STORE, bool COST>
 __global__ __launch_bounds__(256, 2) void wcmap_kernel(const WCMapArgs g) {
     constexpr bool NEED_V = COST || MAP != WC_EUC;   // the storing euclidean pass forms B = M.*S only
-    __shared__ float Ws[2][CBK * CBM];
-    extern __shared__ float Hs[];                    // [2][(CBN + T - 1) * CLDH]
+    __shared__ float Ws[2][RBK * RBM];
+    extern __shared__ float Hs[];                    // recon_lds_bytes(T)
     __shared__ double sh[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-    const long tilesM = (g.m + CBM - 1) / CBM, tilesN = (g.n + CBN - 1) / CBN, tiles = tilesM * tilesN;
-    const int K = g.K, T = g.T, nk = (K + CBK - 1) / CBK;
-    const int hcols = CBN + T - 1, hstage = hcols * CLDH;
+    const long tilesM = (g.m + RBM - 1) / RBM, tilesN = (g.n + RBN - 1) / RBN, tiles = tilesM * tilesN;
+    const int K = g.K, T = g.T, nk = (K + RBK - 1) / RBK;
+    const int hcols = RBN + T - 1, hstage = hcols * RLDH;
     // loaders: consecutive threads along the operand's contiguous dimension (W: i, H: k)
-    const int w_r = tid & (CBM - 1), w_k = tid >> 7;      // + 2 u, u < 8
-    const int h_k = tid & (CBK - 1), h_c = tid >> 4;      // + 16 u
+    const int w_r = tid & (RBM - 1), w_k = tid >> 7;      // + 2 u, u < 8
+    const int h_k = tid & (RBK - 1), h_c = tid >> 4;      // + 16 u
     double part = 0.0;
     for (long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
-        const long i0 = (tl % tilesM) * CBM, j0 = (tl / tilesM) * CBN, jh = j0 - (T - 1);   // jh: the global column of stage column 0
+        const long i0 = (tl % tilesM) * RBM, j0 = (tl / tilesM) * RBN, jh = j0 - (T - 1);   // jh: the global column of stage column 0
         float rw[8], rh[4];
         auto wload = [&](int k0, int t) {
 #pragma unroll
@@ -84,7 +75,7 @@ __global__ __launch_bounds__(256, 2) void wcmap_kernel(const WCMapArgs g) {
         };
         auto wstore = [&](int buf) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) Ws[buf][(w_k + 2 * u) * CBM + w_r] = rw[u];
+            for (int u = 0; u < 8; ++u) Ws[buf][(w_k + 2 * u) * RBM + w_r] = rw[u];
         };
         auto hval = [&](int k0, int c) {   // stage column c of the chunk at k0
             const long j = jh + c;
@@ -103,7 +94,7 @@ __global__ __launch_bounds__(256, 2) void wcmap_kernel(const WCMapArgs g) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int c = 64 * q + h_c + 16 * u;
-                if (c < hcols) Hs[buf * hstage + c * CLDH + h_k] = rh[u];
+                if (c < hcols) Hs[buf * hstage + c * RLDH + h_k] = rh[u];
             }
         };
         f32x16 acc[2];
@@ -124,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void wcmap_kernel(const WCMapArgs g) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int c = h_c + 16 * u;
-            if (c < hcols) Hs[c * CLDH + h_k] = ph[u];
+            if (c < hcols) Hs[c * RLDH + h_k] = ph[u];
         }
         // this lane's elements of M (and V), requested behind the first stage: they arrive under the contraction.
         // acc[y][e]: column (lane & 31) -> i, row (e & 3) + 8 (e >> 2) + 4 (lane >> 5) -> j; an element outside the matrix reads the clamped address of one
@@ -146,16 +137,16 @@ __global__ __launch_bounds__(256, 2) void wcmap_kernel(const WCMapArgs g) {
             const int buf = s & 1, hbuf = kc & 1;
             const bool last_t = t + 1 == T, more = s + 1 < ns, hnext = kc + 1 < nk && 64 * t < hcols;
             const int tn = last_t ? 0 : t + 1, kn = last_t ? kc + 1 : kc;
-            if (more) wload(kn * CBK, tn);
-            if (hnext) hload((kc + 1) * CBK, t);
-            const float *a = Ws[buf], *b = Hs + hbuf * hstage + ((T - 1) - t) * CLDH;
+            if (more) wload(kn * RBK, tn);
+            if (hnext) hload((kc + 1) * RBK, t);
+            const float *a = Ws[buf], *b = Hs + hbuf * hstage + ((T - 1) - t) * RLDH;
 #pragma unroll
-            for (int kk = 0; kk < CBK / 2; ++kk) {
+            for (int kk = 0; kk < RBK / 2; ++kk) {
                 const int k = 2 * kk + lh;
-                const float wf = a[k * CBM + 32 * wv + l31];
+                const float wf = a[k * RBM + 32 * wv + l31];
 #pragma unroll
                 for (int y = 0; y < 2; ++y) {
-                    const float hf = b[(32 * y + l31) * CLDH + k];
+                    const float hf = b[(32 * y + l31) * RLDH + k];
                     acc[y] = __builtin_amdgcn_mfma_f32_32x32x2f32(hf, wf, acc[y], 0, 0, 0);   // D(row = j, col = i)
                 }
             }
@@ -183,11 +174,7 @@ __global__ __launch_bounds__(256, 2) void wcmap_kernel(const WCMapArgs g) {
                     }
                 }
                 if constexpr (COST) {
-                    const double sd = (double)s, vd = (double)v;
-                    double c;
-                    if constexpr (MAP == WC_EUC) { const double d = vd - sd; c = d * d; }              // cnmf.m:241 (0.5 applied to the sum)
-                    else if constexpr (MAP == WC_KL) c = (vd * log(vd / sd) - vd) + sd;                 // cnmf.m:243
-                    else c = (log(sd / vd) + vd / sd) - 1.0;                                            // cnmf.m:245
+                    const double sd = (double)s, vd = (double)v, c = div_term<MAP>(vd, sd);   // cnmf.m:241-245 (euclidean: 0.5 applied to the sum)
                     part += on ? (double)w * c : 0.0;
                 }
             }
@@ -199,12 +186,12 @@ __global__ __launch_bounds__(256, 2) void wcmap_kernel(const WCMapArgs g) {
     }
 }
 
-long wcmap_grid(long m, long n) { return std::min<long>(((m + CBM - 1) / CBM) * ((n + CBN - 1) / CBN), WCMAP_MAX_GRID); }
+long wcmap_grid(long m, long n) { return std::min<long>(((m + RBM - 1) / RBM) * ((n + RBN - 1) / RBN), RECON_MAX_GRID); }
 
 template <int MAP>
 nmfx_status wcmap_launch(hipStream_t st, const WCMapArgs &g, bool store, bool cost) {
     const dim3 grid((unsigned)wcmap_grid(g.m, g.n)), block(256);
-    const size_t lds = wcmap_lds_bytes(g.T);
+    const size_t lds = recon_lds_bytes(g.T);
     if (store && cost) hipLaunchKernelGGL((wcmap_kernel<MAP, true, true>), grid, block, lds, st, g);
     else if (store) hipLaunchKernelGGL((wcmap_kernel<MAP, true, false>), grid, block, lds, st, g);
     else hipLaunchKernelGGL((wcmap_kernel<MAP, false, true>), grid, block, lds, st, g);
@@ -249,7 +236,7 @@ __global__ __launch_bounds__(256) void wc_h_update_kernel(float *H, double *H64,
 nmfx_status run_wcnmf(const nmfx_problem *p, const void *Mhost, nmfx_result *r) {
     TRY(validate_problem(p, r, false, true));
     if (!Mhost) { set_error("wcnmf: the weight matrix M is required"); return NMFX_ERR_INVALID; }
-    if (p->T > WCNMF_MAX_T) { set_error("wcnmf: context length T = %d is not supported (1 .. %d)", p->T, WCNMF_MAX_T); return NMFX_ERR_UNSUPPORTED; }
+    if (p->T > RECON_MAX_T) { set_error("wcnmf: context length T = %d is not supported (1 .. %d)", p->T, RECON_MAX_T); return NMFX_ERR_UNSUPPORTED; }
     if (p->n < p->T - 1) { set_error("wcnmf: n = %ld columns are fewer than T - 1 = %d", (long)p->n, p->T - 1); return NMFX_ERR_INVALID; }
     if (p->n_gpus > 1 || p->multi_backend != 0) { set_error("wcnmf: one GPU only (n_gpus = %d, multi_backend = %d)", p->n_gpus, p->multi_backend); return NMFX_ERR_UNSUPPORTED; }
     int map;

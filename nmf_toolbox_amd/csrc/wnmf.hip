@@ -56,8 +56,8 @@ __global__ __launch_bounds__(256) void wnmf_dev_prepare(const float *V, long ldv
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < count; e += (long)gridDim.x * 256) {
         const long c = e % lead, l = e / lead;
         const MT mv = M[c + ldm * l];
-        const bool on = WWeight<MT>::on(mv);
-        const float w = WWeight<MT>::value(mv);
+        const bool on = Weight<MT>::on(mv);
+        const float w = Weight<MT>::value(mv);
         if (MV) {
             float a = 0.0f;
             if (on) a = w * V[c + ldv * l];

@@ -14,6 +14,7 @@
 #include "api_common.h"
 #include "dev_reduce.h"
 #include "gemm_common.h"
+#include "recon_tile.h"
 
 namespace nmfx {
 namespace {
@@ -32,14 +33,7 @@ struct WMapDevArgs {        // views of V and M with their own leading dimension
     double *partials;       // [gridDim.x] weighted data-fit partials of a cost pass
 };
 
-template <class MT> struct WWeight {   // a weight: observed where it is positive
-    static __device__ __forceinline__ bool on(MT w) { return w > 0.0f; }
-    static __device__ __forceinline__ float value(MT w) { return w; }
-};
-template <> struct WWeight<unsigned char> {   // a byte of a bool / uint8 mask: observed where it is non-zero, weight 1
-    static __device__ __forceinline__ bool on(unsigned char w) { return w != 0; }
-    static __device__ __forceinline__ float value(unsigned char) { return 1.0f; }
-};
+static_assert((int)WM_EUC == (int)NMFX_DIV_EUCLIDEAN && (int)WM_KL == (int)NMFX_DIV_KL && (int)WM_IS == (int)NMFX_DIV_IS, "div_term<MAP> takes the numbering of nmfx_divergence");
 
 template <int MAP, bool STORE, bool COST, int LAYOUT, class MT>
 __global__ __launch_bounds__(256, 2) void wmap_kernel(const WMapDevArgs g) {
@@ -148,8 +142,8 @@ __global__ __launch_bounds__(256, 2) void wmap_kernel(const WMapDevArgs g) {
             for (int e = 0; e < 16; ++e) {
                 long r, j;
                 at(y, e, r, j);
-                const float s = s16[e], v = v16[e], w = WWeight<MT>::value(m16[e]);
-                const bool inside = r < g.m && j < g.n, on = WWeight<MT>::on(m16[e]) && inside;
+                const float s = s16[e], v = v16[e], w = Weight<MT>::value(m16[e]);
+                const bool inside = r < g.m && j < g.n, on = Weight<MT>::on(m16[e]) && inside;
                 const long idx = LAYOUT == 0 ? r + g.lda * j : r * g.lda + j;
                 if constexpr (STORE) {
                     if (inside) {
@@ -159,11 +153,7 @@ __global__ __launch_bounds__(256, 2) void wmap_kernel(const WMapDevArgs g) {
                     }
                 }
                 if constexpr (COST) {
-                    const double sd = (double)s, vd = (double)v;
-                    double c;
-                    if constexpr (MAP == WM_EUC) { const double d = vd - sd; c = d * d; }              // nmf.m:208 (0.5 applied to the sum)
-                    else if constexpr (MAP == WM_KL) c = (vd * log(vd / sd) - vd) + sd;                 // nmf.m:210
-                    else c = (log(sd / vd) + vd / sd) - 1.0;                                            // nmf.m:212
+                    const double sd = (double)s, vd = (double)v, c = div_term<MAP>(vd, sd);   // nmf.m:208-212 (euclidean: 0.5 applied to the sum)
                     part += on ? (double)w * c : 0.0;
                 }
             }

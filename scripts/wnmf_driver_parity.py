@@ -210,11 +210,11 @@ def dump_gpu():
 
 
 # ---- the device code ---------------------------------------------------------------------------------------------------------------------------------------------
-def dump_device(root):
+def dump_device(root, objects=OBJECTS):
     """object -> kernel symbol -> (resource figures, instruction text) of the gfx950 code objects of a built checkout"""
     from kernel_resources import code_objects, kernels
     out = {}
-    for name in OBJECTS:
+    for name in objects:
         obj = os.path.join(root, "nmf_toolbox_amd", "csrc", "_obj", name + ".hip.o")
         figures = {k["name"]: k for k in kernels(obj)}
         for co in code_objects(obj):
@@ -272,24 +272,23 @@ def compare_device(roots):
     return 1 if bad else 0
 
 
-def main(argv):
-    if argv[0] == "dump":
-        kind, root, path = argv[1:4]
-        sys.path[:0] = [os.path.abspath(root), os.path.join(os.path.dirname(HERE), "tests")]
-        import nmf_toolbox_amd
-        assert os.path.abspath(nmf_toolbox_amd.__file__).startswith(os.path.abspath(root) + os.sep), nmf_toolbox_amd.__file__
-        with open(path, "wb") as f:
-            pickle.dump({"abi": dump_abi, "python": dump_python, "gpu": dump_gpu}[kind](), f)
-        return 0
-    assert argv[0] == "compare", __doc__
-    kind, roots = argv[1], argv[2:4]
-    if kind == "device":
-        return compare_device(roots)
+def dump_to(dumps, kind, root, path):
+    """`dump KIND ROOT PATH` of a parity script: the process imports nmf_toolbox_amd from ROOT and pickles dumps[KIND]()"""
+    sys.path[:0] = [os.path.abspath(root), os.path.join(os.path.dirname(HERE), "tests")]
+    import nmf_toolbox_amd
+    assert os.path.abspath(nmf_toolbox_amd.__file__).startswith(os.path.abspath(root) + os.sep), nmf_toolbox_amd.__file__
+    with open(path, "wb") as f:
+        pickle.dump(dumps[kind](), f)
+    return 0
+
+
+def compare_dumps(script, kind, roots):
+    """`script dump KIND ROOT` in a fresh process per side, the two dicts compared case by case -> exit status"""
     got = []
     with tempfile.TemporaryDirectory() as tmp:
         for side, root in zip(("parent", "result"), roots):
             path = os.path.join(tmp, side + ".pkl")
-            subprocess.run([sys.executable, os.path.abspath(__file__), "dump", kind, root, path], check=True)
+            subprocess.run([sys.executable, os.path.abspath(script), "dump", kind, root, path], check=True)
             with open(path, "rb") as f:
                 got.append(pickle.load(f))
     parent, result = got
@@ -302,6 +301,14 @@ def main(argv):
     for k in differ:
         print("DIFFERENT: %s\n  parent: %s\n  result: %s" % (k, show(parent[k]) if k in parent else "-", show(result[k]) if k in result else "-"))
     return 1 if differ else 0
+
+
+def main(argv):
+    if argv[0] == "dump":
+        return dump_to({"abi": dump_abi, "python": dump_python, "gpu": dump_gpu}, *argv[1:4])
+    assert argv[0] == "compare", __doc__
+    kind, roots = argv[1], argv[2:4]
+    return compare_device(roots) if kind == "device" else compare_dumps(__file__, kind, roots)
 
 
 if __name__ == "__main__":
