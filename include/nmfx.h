@@ -400,6 +400,32 @@ nmfx_status nmfx_wnmf_dev(void *stream, int64_t m, int64_t n, int32_t K_total, i
                           const double *W_init_dev, const double *H_init_dev, int32_t maxiter, double tolerance /* < 0: no stop rule */,
                           void *work_dev, size_t work_bytes, float *W_out_dev, float *H_out_dev, double *cost_out_dev /* [maxiter] */,
                           int32_t *iters_run /* host */, int32_t device);
+/* nmfx_wcnmf on operands that already live on the device, on `stream`, out of one work buffer of the caller's: the same update equations,
+ * arithmetic and schedule, and nmfx_wnmf_dev's conventions throughout -- V_dev and M_dev are m x n views with their own leading dimensions in either layout
+ * (layout 0: V[i + ldv*j], the map pass nmfx_wcnmf runs; layout 1: V[i*ldv + j], the MFMA operands of the map pass change places), M float32 weights
+ * (m_kind 0) or bytes (m_kind 1), both read in place and NEVER written, V never looked at where M == 0; the four host vectors travel in kernel arguments.
+ * T is the context length.  W_init_dev is the flat m x K_total*T image, float64: W[i + m*(t*K_total + k)]; H_init_dev is H[k + K_total*j].
+ * Results, all on the device: W_out_dev is the fp32 flat image as it is (layout 0: W[i + m*(t*K_total + k)], a contiguous (T, K_total, m) array) or its
+ * transpose (layout 1: W[i*K_total*T + t*K_total + k], a contiguous (m, T, K_total) array); H_out_dev, cost_out_dev and *iters_run as for nmfx_wnmf_dev.
+ * tolerance < 0 turns the stop rule off: the call then waits for nothing, and it never allocates or frees.
+ * nmfx_wcnmf_dev_work_bytes (host-only) answers the size of work_dev.  With al, g and tiles as above and KT = K_total*T:
+ *   bytes = c*al(4*m*n)                                  mapped operands: c = 1 for kl with float32 weights (B is M itself, read in place), else 2
+ *         + al(8*m*KT) + al(8*K*n)                       float64 masters
+ *         + 3*al(4*m*KT) + al(4*K*n) + 2*al(4*KT*n)      fp32 images; N_all, P_all; Q_A, Q_B
+ *         + al(max(g(m, KT, n), g(KT, n, m)))            GEMM scratch
+ *         + al(8*tiles) + al(8*(3*KT + 2*K)) + al(8*K) + al(2*K)   cost partials; column statistics; lambdas; fixed flags
+ *         + al(8*maxiter) + al(2048*K)                   the cost vector; row-reduction scratch
+ * against 4*m*n*(3 kl | 4 euclidean, is) + KT*(20*m + 8*n) of nmfx_wcnmf: V and M are not held a second time.
+ * NMFX_ERR_INVALID, before any device call: a NULL pointer (the four vectors excepted), a size or maxiter <= 0, T < 1, n < T - 1, ldv or ldm below the
+ * contiguous extent, another layout or m_kind, a divergence that is none of the three, work_bytes below the query's answer.  NMFX_ERR_UNSUPPORTED:
+ * T > 64, NMFX_DIV_AB.  New entry points; no structure grows, so NMFX_VERSION stays 600. */
+nmfx_status nmfx_wcnmf_dev_work_bytes(int64_t m, int64_t n, int32_t K_total, int32_t T, int32_t divergence, int32_t m_kind, int32_t maxiter, size_t *bytes);
+nmfx_status nmfx_wcnmf_dev(void *stream, int64_t m, int64_t n, int32_t K_total, int32_t T, int32_t divergence, int32_t layout /* 0 column-major, 1 row-major */,
+                           const float *V_dev, int64_t ldv, const void *M_dev, int64_t ldm, int32_t m_kind /* 0 float32 weights, 1 bytes (non-zero = 1) */,
+                           const float *lamW, const float *lamH, const uint8_t *fixW, const uint8_t *fixH,   /* host, [K_total] each, or NULL */
+                           const double *W_init_dev, const double *H_init_dev, int32_t maxiter, double tolerance /* < 0: no stop rule */,
+                           void *work_dev, size_t work_bytes, float *W_out_dev, float *H_out_dev, double *cost_out_dev /* [maxiter] */,
+                           int32_t *iters_run /* host */, int32_t device);
 /* The deterministic k-means behind seminmf's default H_init (seminmf.m:109-117: kmeans(V.', K)) on the n columns of X (m x n, dtype): k-means++
  * seeding from the k host uniforms u (the first centre is floor(u[0]*n)), batch Lloyd iterations (at most maxiter), squared Euclidean distance, the
  * 'singleton' rule for empty clusters; tests/seminmf_oracle.py restates every rule.  idx_out [n] receives 0-BASED labels; centroids_out (m x k,

@@ -29,6 +29,7 @@ EXPORTS = [
     "nmfx_engine_between_allreduces", "nmfx_engine_between_allreduces_cost", "nmfx_projfunc_dev", "nmfx_nmfsc_profile", "nmfx_nmfsc_profile_ntags", "nmfx_nmfsc_profile_tag_name", "nmfx_nmfsc_profile_read", "nmfx_last_call_timing", "nmfx_sc_iteration_seconds", "nmfx_engine_cost_lag", "nmfx_engine_sumvv_local", "nmfx_engine_sumvv_set_global",
     "nmfx_minmax_dev", "nmfx_scale_dev", "nmfx_gemm64", "nmfx_engine_sync_master", "nmfx_engine_master_ptrs", "nmfx_engine_init_f64", "nmfx_last_call_exchange", "nmfx_rccl_library", "nmfx_abi_sizes",
     "nmfx_cmfwisa", "nmfx_seminmf", "nmfx_kmeans", "nmfx_nmf_f64", "nmfx_nmf_batch", "nmfx_cnmf_batch", "nmfx_wnmf", "nmfx_wcnmf", "nmfx_wnmf_batch", "nmfx_wcnmf_batch", "nmfx_softmask", "nmfx_softmask_dev", "nmfx_impute", "nmfx_impute_dev", "nmfx_impute_dev_work_bytes", "nmfx_engine_plan", "nmfx_wnmf_dev", "nmfx_wnmf_dev_work_bytes",
+    "nmfx_wcnmf_dev", "nmfx_wcnmf_dev_work_bytes",
 ]
 
 
@@ -129,6 +130,10 @@ def load():
     lib.nmfx_wnmf_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+    lib.nmfx_wcnmf_dev_work_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.nmfx_wcnmf_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     lib.nmfx_cmfwisa.argtypes =[C.POINTER(Problem), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Result), C.c_void_p, C.c_void_p]
     lib.nmfx_kmeans.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.nmfx_constrainednmf.argtypes = [C.POINTER(Problem), C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Result), C.c_void_p]

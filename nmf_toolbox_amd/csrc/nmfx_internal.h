@@ -361,6 +361,31 @@ struct WnmfWork {          // the carve of one work buffer; with base == NULL on
 nmfx_status wnmf_constants(hipStream_t st, const WnmfCall &c, const WnmfWork &wk);               // the operands no pass rewrites; selects on M, never writes V
 nmfx_status wnmf_iterate(hipStream_t st, const WnmfCall &c, const WnmfWork &wk, int *iters_run);   // -> W64, H64, W, H, cost[0, *iters_run)
 
+// ---- wcnmf (wcnmf.hip): the one driver behind nmfx_wcnmf (wcnmf.hip) and nmfx_wcnmf_dev (wcnmf_dev.hip), a third caller of the pattern above ----
+// The view, the summaries and the stop rule are WnmfCall's; W is the flat m x KT image (column t*K + k).  WMap, wnmf_map_of and wnmf_own_b are shared.
+struct WcnmfCall {
+    long m, n;
+    int K, T, map;
+    const float *V;        // the view of (V, M), as in WnmfCall: read in place, never written
+    const void *M;
+    long ldv, ldm;
+    int layout, m_kind;
+    bool all_wf, all_hf, any_lw, any_lh;
+    int maxiter;
+    double tolerance;      // < 0: no stop rule, and then nothing waits for the stream
+};
+struct WcnmfWork {         // the carve of one work buffer; with base == NULL only `bytes` is computed.  gscratch: what gemm_auto may use (>= gemm_scratch_bytes)
+    float *A, *B, *W, *H, *Nw, *Pw, *Qa, *Qb;   // A, B: the mapped operands in V's layout, packed (B is NULL where wnmf_own_b says so); N_all, P_all m x KT; Q_A, Q_B KT x n
+    double *W64, *H64, *parts, *vecs, *cost;    // vecs: sumsq [KT], l1W [KT], csW [KT], l1H [K], wnorm [K]
+    void *scr, *rrs;
+    float *lam;
+    uint8_t *fix;
+    size_t gscratch, bytes;
+    WcnmfWork(void *base, long m, long n, int K, int T, int map, int m_kind, int maxiter, size_t gscratch);
+};
+nmfx_status wcnmf_constants(hipStream_t st, const WcnmfCall &c, const WcnmfWork &wk);               // the operands no pass rewrites; selects on M, never writes V
+nmfx_status wcnmf_iterate(hipStream_t st, const WcnmfCall &c, const WcnmfWork &wk, int *iters_run);   // -> W64, H64, W, H, cost[0, *iters_run)
+
 // ---- Hoyer projection (projfunc.hip): vectors are the COLUMNS of X (len x count), in place ----
 // dir (or dir64, the direction as doubles) != nullptr: the vectors projected are src + mu*dir, formed in fp64 (the line-search step of
 // nmfsc.m:154 / 205 fused into the load); src == nullptr means X itself.  X receives the result.

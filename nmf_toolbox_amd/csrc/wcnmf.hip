@@ -1,4 +1,4 @@
-// Weighted convolutive NMF: nmfx_wcnmf.  cnmf.m:155-258 with every element of the data fit weighted by M >= 0 (m x n, the shape of V).  0-based, T = context
+// Weighted convolutive NMF: nmfx_wcnmf, and the driver it shares with nmfx_wcnmf_dev.  cnmf.m:155-258 with every element of the data fit weighted by M >= 0 (m x n, the shape of V).  0-based, T = context
 // length, S = sum_t W_t * rshift_t(H), rshift_t(H)(:, j) = H(:, j - t) (0 for j < t):
 //     divergence   A             B        d(V, S)
 //     euclidean    M.*V          M.*S     0.5*(V - S).^2
@@ -15,198 +15,38 @@
 // past the end count as weight 1: with M == 1 that is the reference's sum_t cs(W_t) everywhere.  It is added by the H update as the tail term
 // sum_{t : j + t >= n} cs(W_t)(k), from the float64 column sums of the master.
 //
-// Device state, schedule and second products are wnmf's (wnmf.hip): V, M, A, B as fp32 m x n (B = M itself for kl), W (the flat m x KT image, column t*K + k)
-// and H as float64 masters with fp32 images, one stream, no atomics; the cost of iteration t is the by-product of the map pass that opens t + 1, plus one
-// cost-only pass at the end; with the stop rule on the host reads 8 bytes before the W update is launched.  The call holds 4*m*n*(3 kl | 4 euclidean, is) +
-// KT*(20*m + 8*n) bytes (the W master, its image, N_all, P_all; Q_A, Q_B) plus O((m + n)*K).  Second products on the pipelined GEMM: N_all = A*H_stack',
-// P_all = B*H_stack' (m x KT, VIEW_HSTACK_RC) and Q_A = W_flat'*A, Q_B = W_flat'*B (KT x n); the H update (wc_h_update_kernel) does the shift-sum of both,
-// the kl tail and the float64 update in one launch.
-//
-// The convolutive weighted map pass (wcmap_kernel) forms S on the reconstruction tile that recon_tile.h describes -- 128 x 64 of S per workgroup, the
-// contraction over (k-chunk, t) with the H stage and its halo loaded once per chunk; the staging, the LDS layout and its bank argument are described there,
-// and its constants, LDS size and limit on T are the header's -- in the column-major layout, so that the epilogue's lanes run along i; V and M requested
-// behind the opening stages, clamped addresses outside the matrix; the rolled two-block element map of wmap_kernel (wnmf_pass.h), the A / B stores, float64
-// cost terms, one float64 partial per workgroup.  THE KERNEL KEEPS ITS OWN TEXT OF THE CONTRACTION: on recon_contract (with a callable behind the opening
-// stages, or split into open / run halves) the results were the same bits, but three to four of its nine instantiations were 1 to 5 % slower per launch,
-// outside the parent's own spread (profiles/refactor_recon_tile.md).  A change to recon_contract's staging has to be made here too.
+// One driver, two entries (wnmf.hip's pattern, a third caller of it).  wcnmf_constants and wcnmf_iterate below are the whole fit on a VIEW of (V, M) -- a
+// pointer, a layout, two leading dimensions and the kind of M's element (WcnmfCall) -- out of one carved work buffer (WcnmfWork), on any stream.  nmfx_wcnmf
+// (here) uploads packed column-major fp32 copies of V and M and hands them over as a view with layout 0, ldv = ldm = m and float weights on the null stream;
+// nmfx_wcnmf_dev (wcnmf_dev.hip) hands over the caller's tensors as they are.  Neither entry has a loop of its own.
+// Device state: V and M as fp32 (or M as bytes), read in place and never written; W (the flat m x KT image, column t*K + k) and H as float64 masters with
+// fp32 images; the mapped operands A and B as fp32 m x n in V's layout, packed.  The constant ones are formed once per call by wcnmf_constants
+// (weighted_constants.h's kernel, which selects on M and never multiplies a masked V): A = on ? w*v : 0 for euclidean, and for kl B is M itself (float weights)
+// or the fp32 on ? 1 : 0 of a byte mask.  One stream, no atomics.  nmfx_wcnmf holds 4*m*n*(3 kl | 4 euclidean, is) + KT*(20*m + 8*n) bytes (the W master,
+// its image, N_all, P_all; Q_A, Q_B) plus O((m + n)*K): V, M and one work buffer.
+// The map pass is wcmap_kernel (wcnmf_pass.h).  Second products on the pipelined GEMM: N_all = A*H_stack', P_all = B*H_stack' (m x KT, VIEW_HSTACK_RC) and
+// Q_A = W_flat'*A, Q_B = W_flat'*B (KT x n); they read A and B through the GEMM view that matches the layout: a column-major m x n operand is
+// output-contiguous (VIEW_RC) for the W step and contraction-contiguous (VIEW_KC) for the H step, a row-major one the other way round; where B is M itself
+// it is read with M's own leading dimension.  The H update (wc_h_update_kernel) does the shift-sum of both Q products, the kl tail and the float64 update in
+// one launch; Q_A and Q_B are the GEMM's outputs, whatever V's layout.
+// Schedule (wnmf's): the cost of iteration t is the by-product of the map pass that opens t + 1, plus one cost-only pass at the end; with the stop rule on,
+// the host reads those 8 bytes (one hipMemcpyAsync + hipStreamSynchronize on the call's stream, the last two costs kept on the host) BEFORE the W update of
+// t + 1 is launched, so a stop returns W(t), H(t) without a spare copy.  With the rule off nothing waits, allocates or frees.
 #include "api_common.h"
 #include "dev_reduce.h"
 #include "gemm_common.h"
-#include "recon_tile.h"
+#include "weighted_constants.h"
+#include "wcnmf_pass.h"
 
 namespace nmfx {
 namespace {
 
-enum WCMap { WC_EUC = NMFX_DIV_EUCLIDEAN, WC_KL = NMFX_DIV_KL, WC_IS = NMFX_DIV_IS };   // (div_term's numbering)
-
-struct WCMapArgs {
-    const float *W, *H;     // fp32 images: W[i + m*(t*K + k)], H[k + K*j]
-    const float *V, *M;     // m x n
-    float *A, *B;           // m x n outputs of a storing pass (either may be NULL: not needed by the divergence)
-    long m, n;
-    int K, T;
-    double *partials;       // [gridDim.x] weighted data-fit partials of a cost pass
-};
-
-template <int MAP, bool STORE, bool COST>
-__global__ __launch_bounds__(256, 2) void wcmap_kernel(const WCMapArgs g) {
-    constexpr bool NEED_V = COST || MAP != WC_EUC;   // the storing euclidean pass forms B = M.*S only
-    __shared__ float Ws[2][RBK * RBM];
-    extern __shared__ float Hs[];                    // recon_lds_bytes(T)
-    __shared__ double sh[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-    const long tilesM = (g.m + RBM - 1) / RBM, tilesN = (g.n + RBN - 1) / RBN, tiles = tilesM * tilesN;
-    const int K = g.K, T = g.T, nk = (K + RBK - 1) / RBK;
-    const int hcols = RBN + T - 1, hstage = hcols * RLDH;
-    // loaders: consecutive threads along the operand's contiguous dimension (W: i, H: k)
-    const int w_r = tid & (RBM - 1), w_k = tid >> 7;      // + 2 u, u < 8
-    const int h_k = tid & (RBK - 1), h_c = tid >> 4;      // + 16 u
-    double part = 0.0;
-    for (long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
-        const long i0 = (tl % tilesM) * RBM, j0 = (tl / tilesM) * RBN, jh = j0 - (T - 1);   // jh: the global column of stage column 0
-        float rw[8], rh[4];
-        auto wload = [&](int k0, int t) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const long i = i0 + w_r;
-                const int k = k0 + w_k + 2 * u;
-                rw[u] = (i < g.m && k < K) ? g.W[i + g.m * ((long)t * K + k)] : 0.0f;
-            }
-        };
-        auto wstore = [&](int buf) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) Ws[buf][(w_k + 2 * u) * RBM + w_r] = rw[u];
-        };
-        auto hval = [&](int k0, int c) {   // stage column c of the chunk at k0
-            const long j = jh + c;
-            const int k = k0 + h_k;
-            return (j >= 0 && j < g.n && k < K) ? g.H[k + (long)K * j] : 0.0f;
-        };
-        // slice q of a chunk's H stage: stage columns 64 q + h_c + 16 u, u < 4
-        auto hload = [&](int k0, int q) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int c = 64 * q + h_c + 16 * u;
-                rh[u] = c < hcols ? hval(k0, c) : 0.0f;
-            }
-        };
-        auto hstore = [&](int buf, int q) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int c = 64 * q + h_c + 16 * u;
-                if (c < hcols) Hs[buf * hstage + c * RLDH + h_k] = rh[u];
-            }
-        };
-        f32x16 acc[2];
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[y][e] = 0.0f;
-        // the first stages: W_0 of chunk 0 and the whole H stage of chunk 0, halo included (8 x 16 columns >= 64 + T - 1 for T <= 64); every load is issued
-        // before the first store, so a tile opens with one trip to memory, not one per 16 columns
-        float ph[8];
-        wload(0, 0);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int c = h_c + 16 * u;
-            ph[u] = c < hcols ? hval(0, c) : 0.0f;
-        }
-        wstore(0);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int c = h_c + 16 * u;
-            if (c < hcols) Hs[c * RLDH + h_k] = ph[u];
-        }
-        // this lane's elements of M (and V), requested behind the first stage: they arrive under the contraction.
-        // acc[y][e]: column (lane & 31) -> i, row (e & 3) + 8 (e >> 2) + 4 (lane >> 5) -> j; an element outside the matrix reads the clamped address of one
-        // inside (wmap_kernel's reason: 32 live predicates are 64 scalar registers), the epilogue skips it
-        const long i = i0 + 32 * wv + l31, ic = i < g.m ? i : g.m - 1;
-        f32x16 vreg[2], mreg[2];
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const long j = j0 + 32 * y + (e & 3) + 8 * (e >> 2) + 4 * lh, jc = j < g.n ? j : g.n - 1;
-                mreg[y][e] = g.M[ic + g.m * jc];
-                vreg[y][e] = NEED_V ? g.V[ic + g.m * jc] : 0.0f;
-            }
-        __builtin_amdgcn_sched_barrier(0);   // (or the compiler sinks every one of them to its first use)
-        __syncthreads();
-        int t = 0, kc = 0;
-        for (int s = 0, ns = nk * T; s < ns; ++s) {
-            const int buf = s & 1, hbuf = kc & 1;
-            const bool last_t = t + 1 == T, more = s + 1 < ns, hnext = kc + 1 < nk && 64 * t < hcols;
-            const int tn = last_t ? 0 : t + 1, kn = last_t ? kc + 1 : kc;
-            if (more) wload(kn * RBK, tn);
-            if (hnext) hload((kc + 1) * RBK, t);
-            const float *a = Ws[buf], *b = Hs + hbuf * hstage + ((T - 1) - t) * RLDH;
-#pragma unroll
-            for (int kk = 0; kk < RBK / 2; ++kk) {
-                const int k = 2 * kk + lh;
-                const float wf = a[k * RBM + 32 * wv + l31];
-#pragma unroll
-                for (int y = 0; y < 2; ++y) {
-                    const float hf = b[(32 * y + l31) * RLDH + k];
-                    acc[y] = __builtin_amdgcn_mfma_f32_32x32x2f32(hf, wf, acc[y], 0, 0, 0);   // D(row = j, col = i)
-                }
-            }
-            if (more) wstore(buf ^ 1);          // (the other buffer: last read one trip ago, behind the barrier below)
-            if (hnext) hstore(hbuf ^ 1, t);     // (the other H buffer: last read in the chunk before this one)
-            __syncthreads();
-            t = tn; kc = kn;
-        }
-        // The rolled two-block epilogue of wmap_kernel: the second accumulator block moves into the first one's place
-#pragma unroll 1
-        for (int y = 0; y < 2; ++y) {
-            const f32x16 s16 = acc[0], v16 = vreg[0], m16 = mreg[0];
-            acc[0] = acc[1]; vreg[0] = vreg[1]; mreg[0] = mreg[1];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const long j = j0 + 32 * y + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                const float s = s16[e], v = v16[e], w = m16[e];
-                const bool on = w > 0.0f && i < g.m && j < g.n;
-                const long idx = i + g.m * j;
-                if constexpr (STORE) {
-                    if (i < g.m && j < g.n) {
-                        if constexpr (MAP == WC_EUC) g.B[idx] = on ? w * s : 0.0f;
-                        else if constexpr (MAP == WC_KL) g.A[idx] = on ? (w * v) / s : 0.0f;
-                        else { g.A[idx] = on ? (w * v) / (s * s) : 0.0f; g.B[idx] = on ? w / s : 0.0f; }
-                    }
-                }
-                if constexpr (COST) {
-                    const double sd = (double)s, vd = (double)v, c = div_term<MAP>(vd, sd);   // cnmf.m:241-245 (euclidean: 0.5 applied to the sum)
-                    part += on ? (double)w * c : 0.0;
-                }
-            }
-        }
-    }
-    if constexpr (COST) {
-        part = block_sum256(part, sh);
-        if (tid == 0) g.partials[blockIdx.x] = part;
-    }
-}
-
-long wcmap_grid(long m, long n) { return std::min<long>(((m + RBM - 1) / RBM) * ((n + RBN - 1) / RBN), RECON_MAX_GRID); }
-
-template <int MAP>
-nmfx_status wcmap_launch(hipStream_t st, const WCMapArgs &g, bool store, bool cost) {
-    const dim3 grid((unsigned)wcmap_grid(g.m, g.n)), block(256);
-    const size_t lds = recon_lds_bytes(g.T);
-    if (store && cost) hipLaunchKernelGGL((wcmap_kernel<MAP, true, true>), grid, block, lds, st, g);
-    else if (store) hipLaunchKernelGGL((wcmap_kernel<MAP, true, false>), grid, block, lds, st, g);
-    else hipLaunchKernelGGL((wcmap_kernel<MAP, false, true>), grid, block, lds, st, g);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
-}
-
-// ingest: V <- 0 where M == 0 (whatever was there: NaN, Inf, negative), and the constant operand M.*V of the euclidean maps
-__global__ __launch_bounds__(256) void wcnmf_prepare(float *V, const float *M, float *MV, long count) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < count; e += (long)gridDim.x * 256) {
-        const float w = M[e];
-        const bool on = w > 0.0f;
-        const float v = on ? V[e] : 0.0f;
-        if (!on) V[e] = 0.0f;
-        if (MV) MV[e] = on ? w * v : 0.0f;
+template <int LAYOUT, class MT>
+nmfx_status wcmap_dispatch(int map, hipStream_t st, const WCMapArgs &g, bool store, bool cost) {
+    switch (map) {
+        case WM_EUC: return wcmap_launch<WM_EUC, LAYOUT, MT>(st, g, store, cost);
+        case WM_KL: return wcmap_launch<WM_KL, LAYOUT, MT>(st, g, store, cost);
+        default: return wcmap_launch<WM_IS, LAYOUT, MT>(st, g, store, cost);
     }
 }
 
@@ -239,56 +79,95 @@ nmfx_status run_wcnmf(const nmfx_problem *p, const void *Mhost, nmfx_result *r) 
     if (p->T > RECON_MAX_T) { set_error("wcnmf: context length T = %d is not supported (1 .. %d)", p->T, RECON_MAX_T); return NMFX_ERR_UNSUPPORTED; }
     if (p->n < p->T - 1) { set_error("wcnmf: n = %ld columns are fewer than T - 1 = %d", (long)p->n, p->T - 1); return NMFX_ERR_INVALID; }
     if (p->n_gpus > 1 || p->multi_backend != 0) { set_error("wcnmf: one GPU only (n_gpus = %d, multi_backend = %d)", p->n_gpus, p->multi_backend); return NMFX_ERR_UNSUPPORTED; }
-    int map;
-    switch (p->divergence) {
-        case NMFX_DIV_EUCLIDEAN: map = WC_EUC; break;
-        case NMFX_DIV_KL: map = WC_KL; break;
-        case NMFX_DIV_IS: map = WC_IS; break;
-        case NMFX_DIV_AB: set_error("wcnmf: the alpha-beta divergence is not supported (euclidean, kl, is)"); return NMFX_ERR_UNSUPPORTED;
-        default: set_error("wcnmf: divergence %d has no weighted update equations", p->divergence); return NMFX_ERR_INVALID;
-    }
+    if (p->divergence == NMFX_DIV_AB) { set_error("wcnmf: the alpha-beta divergence is not supported (euclidean, kl, is)"); return NMFX_ERR_UNSUPPORTED; }
+    const int map = wnmf_map_of(p->divergence);
+    if (map < 0) { set_error("wcnmf: divergence %d has no weighted update equations", p->divergence); return NMFX_ERR_INVALID; }
     DeviceGuard dg_;
     TRY(single_gpu_device(p));
     const long m = p->m, n = p->n;
     const int K = p->K_total, T = p->T, KT = K * T;
-    const size_t mn = (size_t)m * n, mKT = (size_t)m * KT, Kn = (size_t)K * n, KTn = (size_t)KT * n;
+    const size_t mn = (size_t)m * n, mKT = (size_t)m * KT, Kn = (size_t)K * n;
     const SourceVectors<float> src = expand_sources<float>(p, K);
-    const bool all_wf = src.all_wf, all_hf = src.all_hf, any_lw = src.any_lw, any_lh = src.any_lh;
-    const bool own_b = map != WC_KL;   // euclidean: A = M.*V (constant), B per pass; kl: A per pass, B = M itself; is: both per pass
     const size_t gscratch = std::max(gemm_scratch_bytes(m, KT, n), gemm_scratch_bytes(KT, n, m));
-    const long np = wcmap_grid(m, n);
-    DevBuf Vd, Md, Ad, Bd, W64d, H64d, W32d, H32d, Nw, Pw, Qa, Qb, scr, parts, vecs, lamd, fixd, dcost, rrs;
+    DevBuf Vd, Md, work;
     TRY(Vd.alloc(mn * 4)); TRY(Md.alloc(mn * 4));
-    TRY(Ad.alloc(mn * 4));
-    if (own_b) TRY(Bd.alloc(mn * 4));
-    TRY(W64d.alloc(mKT * 8)); TRY(H64d.alloc(Kn * 8)); TRY(W32d.alloc(mKT * 4)); TRY(H32d.alloc(Kn * 4));
-    TRY(Nw.alloc(mKT * 4)); TRY(Pw.alloc(mKT * 4)); TRY(Qa.alloc(KTn * 4)); TRY(Qb.alloc(KTn * 4));
-    TRY(scr.alloc(gscratch)); TRY(parts.alloc((size_t)np * 8)); TRY(vecs.alloc(((size_t)3 * KT + 2 * K) * 8));
-    TRY(lamd.alloc((size_t)2 * K * 4)); TRY(fixd.alloc((size_t)2 * K)); TRY(dcost.alloc((size_t)p->maxiter * 8));
-    TRY(rrs.alloc(row_reduce_scratch_bytes(K)));
-    float *V = Vd.as<float>(), *M = Md.as<float>(), *A = Ad.as<float>(), *B = own_b ? Bd.as<float>() : M;
-    double *W64 = W64d.as<double>(), *H64 = H64d.as<double>();
-    float *W = W32d.as<float>(), *H = H32d.as<float>();
-    double *sumsq = vecs.as<double>(), *l1W = sumsq + KT, *csW = sumsq + 2 * KT, *l1H = sumsq + 3 * KT, *wnorm = l1H + K;
-    float *lamW = lamd.as<float>(), *lamH = lamW + K;
-    uint8_t *fixW = fixd.as<uint8_t>(), *fixH = fixW + K;
+    TRY(work.alloc(WcnmfWork(nullptr, m, n, K, T, map, 0, p->maxiter, gscratch).bytes));
+    const WcnmfWork wk(work.p, m, n, K, T, map, 0, p->maxiter, gscratch);
+    WcnmfCall c{};
+    c.m = m; c.n = n; c.K = K; c.T = T; c.map = map;
+    c.V = Vd.as<float>(); c.M = Md.p; c.ldv = c.ldm = m; c.layout = 0; c.m_kind = 0;   // packed column-major fp32 copies
+    c.all_wf = src.all_wf; c.all_hf = src.all_hf; c.any_lw = src.any_lw; c.any_lh = src.any_lh;
+    c.maxiter = p->maxiter; c.tolerance = p->tolerance;
     hipStream_t st = nullptr;
     StreamDrain drain_(st);
     CallClock clock;
-    NMFX_HIP(hipMemcpyAsync(lamW, src.lw.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(lamH, src.lh.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(fixW, src.fw.data(), (size_t)K, hipMemcpyHostToDevice, st));
-    NMFX_HIP(hipMemcpyAsync(fixH, src.fh.data(), (size_t)K, hipMemcpyHostToDevice, st));
-    TRY(upload(st, p->V, p->dtype, V, mn, 1.0));
-    TRY(upload(st, Mhost, p->dtype, M, mn, 1.0));
-    TRY(ingest_master(st, p->W_init, p->dtype, W64, W, mKT));
-    TRY(ingest_master(st, p->H_init, p->dtype, H64, H, Kn));
-    hipLaunchKernelGGL(wcnmf_prepare, dim3(grid1((long)mn)), dim3(256), 0, st, V, M, map == WC_EUC ? A : nullptr, (long)mn);
-    NMFX_HIP(hipGetLastError());
+    NMFX_HIP(hipMemcpyAsync(wk.lam, src.lw.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(wk.lam + K, src.lh.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(wk.fix, src.fw.data(), (size_t)K, hipMemcpyHostToDevice, st));
+    NMFX_HIP(hipMemcpyAsync(wk.fix + K, src.fh.data(), (size_t)K, hipMemcpyHostToDevice, st));
+    TRY(upload(st, p->V, p->dtype, Vd.as<float>(), mn, 1.0));
+    TRY(upload(st, Mhost, p->dtype, Md.as<float>(), mn, 1.0));
+    TRY(ingest_master(st, p->W_init, p->dtype, wk.W64, wk.W, mKT));
+    TRY(ingest_master(st, p->H_init, p->dtype, wk.H64, wk.H, Kn));
+    TRY(wcnmf_constants(st, c, wk));
     NMFX_HIP(hipStreamSynchronize(st));   // (the caller's pageable buffers and the host vectors above have been read)
     clock.end(&IoStats::ingest_s);
 
-    auto col_sums = [&]() -> nmfx_status { return map == WC_KL ? col_reduce64(st, W64, m, m, KT, 0, csW) : NMFX_OK; };   // cs(W_t) of the kl tail term
+    int it = 0;
+    TRY(wcnmf_iterate(st, c, wk, &it));
+    NMFX_HIP(hipMemcpy(r->cost, wk.cost, (size_t)it * 8, hipMemcpyDeviceToHost));
+    r->cost_len = r->iters_run = it;
+    clock.end(&IoStats::iterate_s);
+    TRY(egress_master(st, wk.W64, wk.W, p->dtype, r->W, mKT));
+    NMFX_HIP(hipStreamSynchronize(st));
+    TRY(egress_master(st, wk.H64, wk.H, p->dtype, r->H, Kn));
+    NMFX_HIP(hipStreamSynchronize(st));
+    clock.end(&IoStats::egress_s);
+    return NMFX_OK;
+}
+
+}  // namespace
+
+WcnmfWork::WcnmfWork(void *base, long m, long n, int K, int T, int map, int m_kind, int maxiter, size_t gscratch_) {
+    const size_t KT = (size_t)K * T, mn = (size_t)m * n, mKT = (size_t)m * KT, Kn = (size_t)K * n, KTn = KT * n;
+    Carver c(base);
+    A = c.take<float>(mn);
+    B = wnmf_own_b(map, m_kind) ? c.take<float>(mn) : nullptr;
+    W64 = c.take<double>(mKT); H64 = c.take<double>(Kn);
+    W = c.take<float>(mKT); H = c.take<float>(Kn);
+    Nw = c.take<float>(mKT); Pw = c.take<float>(mKT); Qa = c.take<float>(KTn); Qb = c.take<float>(KTn);
+    gscratch = gscratch_;
+    scr = c.take<char>(gscratch);
+    parts = c.take<double>((size_t)wcmap_grid(m, n));
+    vecs = c.take<double>(3 * KT + 2 * (size_t)K);
+    lam = c.take<float>((size_t)2 * K);
+    fix = c.take<uint8_t>((size_t)2 * K);
+    cost = c.take<double>((size_t)maxiter);
+    rrs = c.take<char>(row_reduce_scratch_bytes(K));
+    bytes = c.off;
+}
+
+nmfx_status wcnmf_constants(hipStream_t st, const WcnmfCall &c, const WcnmfWork &wk) {
+    const long lead = c.layout == 0 ? c.m : c.n, lines = c.layout == 0 ? c.n : c.m;   // the contiguous extent, and the one the leading dimension steps over
+    float *MV = c.map == WM_EUC ? wk.A : nullptr, *Bf = (c.map == WM_KL && wnmf_own_b(c.map, c.m_kind)) ? wk.B : nullptr;
+    return weighted_constants(st, c.V, c.ldv, c.M, c.ldm, c.m_kind, MV, Bf, lead, lines);   // (weighted_constants.h)
+}
+
+nmfx_status wcnmf_iterate(hipStream_t st, const WcnmfCall &c, const WcnmfWork &wk, int *iters_run) {
+    const long m = c.m, n = c.n, lead = c.layout == 0 ? m : n;
+    const int K = c.K, T = c.T, KT = K * T, map = c.map;
+    const size_t Kn = (size_t)K * n;
+    const bool all_wf = c.all_wf, all_hf = c.all_hf, any_lw = c.any_lw, any_lh = c.any_lh;
+    float *A = wk.A, *W = wk.W, *H = wk.H;
+    const bool own_b = wnmf_own_b(map, c.m_kind);   // euclidean: A = M.*V (constant), B per pass; kl: A per pass, B = M (itself, or its fp32 0 / 1); is: both per pass
+    const float *B = own_b ? wk.B : static_cast<const float *>(c.M);
+    const long ldb = own_b ? lead : c.ldm;
+    double *W64 = wk.W64, *H64 = wk.H64, *sumsq = wk.vecs, *l1W = sumsq + KT, *csW = sumsq + 2 * KT, *l1H = sumsq + 3 * KT, *wnorm = l1H + K;
+    float *lamW = wk.lam, *lamH = lamW + K;
+    uint8_t *fixW = wk.fix, *fixH = fixW + K;
+    const long np = wcmap_grid(m, n);
+
+    auto col_sums = [&]() -> nmfx_status { return map == WM_KL ? col_reduce64(st, W64, m, m, KT, 0, csW) : NMFX_OK; };   // cs(W_t) of the kl tail term
     TRY(col_reduce64(st, W64, m, m, KT, 1, sumsq));                                   // cnmf.m:157-166: every source, fixed ones included
     TRY(w_normalize(st, W, m, K, T, sumsq, nullptr, 1, wnorm, 0, W64));
     TRY(scale_rows64(st, H64, H, K, n, wnorm));
@@ -296,52 +175,53 @@ nmfx_status run_wcnmf(const nmfx_problem *p, const void *Mhost, nmfx_result *r) 
     // S in registers -> the mapped operands and / or the weighted data-fit partials of the current (W, H)
     auto s_map = [&](bool store, bool cost) -> nmfx_status {
         WCMapArgs g{};
-        g.W = W; g.H = H; g.V = V; g.M = M; g.m = m; g.n = n; g.K = K; g.T = T;
-        g.A = map == WC_EUC ? nullptr : A; g.B = map == WC_KL ? nullptr : B;
-        g.partials = parts.as<double>();
-        switch (map) {
-            case WC_EUC: return wcmap_launch<WC_EUC>(st, g, store, cost);
-            case WC_KL: return wcmap_launch<WC_KL>(st, g, store, cost);
-            default: return wcmap_launch<WC_IS>(st, g, store, cost);
-        }
+        g.W = W; g.H = H; g.V = c.V; g.M = c.M; g.m = m; g.n = n; g.K = K; g.T = T;
+        g.ldv = c.ldv; g.ldm = c.ldm; g.lda = lead;
+        g.A = map == WM_EUC ? nullptr : A; g.B = map == WM_KL ? nullptr : wk.B;
+        g.partials = wk.parts;
+        if (c.layout == 0) return c.m_kind ? wcmap_dispatch<0, unsigned char>(map, st, g, store, cost) : wcmap_dispatch<0, float>(map, st, g, store, cost);
+        return c.m_kind ? wcmap_dispatch<1, unsigned char>(map, st, g, store, cost) : wcmap_dispatch<1, float>(map, st, g, store, cost);
     };
     auto cost_of_pass = [&](int idx) -> nmfx_status {   // cost[idx] of the state the last s_map(., true) saw (cnmf.m:239-251)
         if (any_lw) TRY(col_reduce(st, W, m, m, KT, 2, l1W));
-        if (any_lh) TRY(row_reduce(st, H, K, K, n, 2, l1H, rrs.p));
-        return finish_cost(st, parts.as<double>(), (int)np, map == WC_EUC ? 0.5 : 1.0, any_lw ? l1W : nullptr, KT, lamW, any_lh ? l1H : nullptr, K, lamH,
-                           dcost.as<double>() + idx);
+        if (any_lh) TRY(row_reduce(st, H, K, K, n, 2, l1H, wk.rrs));
+        return finish_cost(st, wk.parts, (int)np, map == WM_EUC ? 0.5 : 1.0, any_lw ? l1W : nullptr, KT, lamW, any_lh ? l1H : nullptr, K, lamH, wk.cost + idx);
     };
     auto product = [&](long Mo, long No, long Kc, OpView a, OpView b, float *C) -> nmfx_status {
         GemmParams g;
         memset(&g, 0, sizeof(g));
         g.M = Mo; g.N = No; g.Kc = Kc; g.A = a; g.B = b; g.C = C; g.ldc = Mo; g.epi = EPI_STORE; g.splitk = 1;
-        return gemm_auto(st, g, scr.p, gscratch);
+        return gemm_auto(st, g, wk.scr, wk.gscratch);
     };
-    auto rc = [&](const float *X) { return OpView{X, nullptr, m, VIEW_RC, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f}; };
-    auto kc = [&](const float *X) { return OpView{X, nullptr, m, VIEW_KC, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f}; };
+    // an m x n operand in the call's layout: output-contiguous for the W step and contraction-contiguous for the H step when column-major, the other way
+    // round when row-major
+    const int w_mode = c.layout == 0 ? VIEW_RC : VIEW_KC, h_mode = c.layout == 0 ? VIEW_KC : VIEW_RC;
+    auto mn_view = [&](const float *X, long ld, int mode) { return OpView{X, nullptr, ld, mode, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f}; };
+    const OpView w_kc{W, nullptr, m, VIEW_KC, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f};
     const OpView h_stack = T == 1 ? OpView{H, nullptr, (long)K, VIEW_RC, 0, 0, 0, NMFX_PRO_NONE, 0.f, 0.f}
                                   : OpView{H, nullptr, (long)K, VIEW_HSTACK_RC, K, 0, 0, NMFX_PRO_NONE, 0.f, 0.f};   // r = (t, k): H(k, kc - t)
     auto w_step = [&]() -> nmfx_status {
-        TRY(product(m, KT, n, rc(A), h_stack, Nw.as<float>()));   // N_all = A*H_stack'
-        TRY(product(m, KT, n, rc(B), h_stack, Pw.as<float>()));   // P_all = B*H_stack'
+        TRY(product(m, KT, n, mn_view(A, lead, w_mode), h_stack, wk.Nw));   // N_all = A*H_stack'
+        TRY(product(m, KT, n, mn_view(B, ldb, w_mode), h_stack, wk.Pw));    // P_all = B*H_stack'
         WUpdateParams u{};
-        u.W = W; u.W64 = W64; u.N = Nw.as<float>(); u.P = Pw.as<float>(); u.lamW = lamW; u.fixW = fixW; u.m = m; u.K = K; u.T = T;
+        u.W = W; u.W64 = W64; u.N = wk.Nw; u.P = wk.Pw; u.lamW = lamW; u.fixW = fixW; u.m = m; u.K = K; u.T = T;
         u.sumsq = sumsq; u.inv_exp = 1.0f; u.rule = 0; u.n_chunks = 1; u.fuse_norm = 0;   // cnmf.m:193 in double on the master, per (k, t) column
         TRY(w_update(st, u));
         TRY(w_normalize(st, W, m, K, T, sumsq, fixW, 1, nullptr, 0, W64));                // cnmf.m:196-199: H is not rescaled
         return col_sums();
     };
     auto h_step = [&]() -> nmfx_status {
-        TRY(product(KT, n, m, kc(W), kc(A), Qa.as<float>()));   // Q_A = W_flat'*A
-        TRY(product(KT, n, m, kc(W), kc(B), Qb.as<float>()));   // Q_B = W_flat'*B
-        hipLaunchKernelGGL(wc_h_update_kernel, dim3((unsigned)((Kn + 255) / 256)), dim3(256), 0, st, H, H64, Qa.as<float>(), Qb.as<float>(),
-                           map == WC_KL ? csW : nullptr, K, T, n, lamH, fixH);
+        TRY(product(KT, n, m, w_kc, mn_view(A, lead, h_mode), wk.Qa));   // Q_A = W_flat'*A
+        TRY(product(KT, n, m, w_kc, mn_view(B, ldb, h_mode), wk.Qb));    // Q_B = W_flat'*B
+        hipLaunchKernelGGL(wc_h_update_kernel, dim3((unsigned)((Kn + 255) / 256)), dim3(256), 0, st, H, H64, wk.Qa, wk.Qb, map == WM_KL ? csW : nullptr, K, T, n,
+                           lamH, fixH);
         NMFX_HIP(hipGetLastError());
         return NMFX_OK;
     };
     int it = 0;
     bool stopped = false;
-    for (; it < p->maxiter; ++it) {
+    double prev = 0.0, cur = 0.0;
+    for (; it < c.maxiter; ++it) {
         // the pass that opens iteration it + 1: the mapped operands of (W(it), H(it)) and, from the second iteration on, the cost of iteration it
         bool maps_current = false;
         if (it > 0 || !all_wf) {
@@ -351,9 +231,12 @@ nmfx_status run_wcnmf(const nmfx_problem *p, const void *Mhost, nmfx_result *r) 
         }
         if (it > 0) {
             TRY(cost_of_pass(it - 1));
-            if (p->tolerance >= 0) {
-                NMFX_HIP(hipMemcpy(&r->cost[it - 1], dcost.as<double>() + (it - 1), 8, hipMemcpyDeviceToHost));
-                if (mu_stop(0, r->cost, it - 1, p->tolerance)) { stopped = true; break; }   // cnmf.m:254-257: W(it), H(it) are still in place
+            if (c.tolerance >= 0) {
+                prev = cur;
+                NMFX_HIP(hipMemcpyAsync(&cur, wk.cost + (it - 1), 8, hipMemcpyDeviceToHost, st));
+                NMFX_HIP(hipStreamSynchronize(st));
+                const double pair[2] = {prev, cur};
+                if (it - 1 > 0 && mu_stop(0, pair, 1, c.tolerance)) { stopped = true; break; }   // cnmf.m:254-257: W(it), H(it) are still in place
             }
         }
         if (!all_wf) {
@@ -367,20 +250,12 @@ nmfx_status run_wcnmf(const nmfx_problem *p, const void *Mhost, nmfx_result *r) 
     }
     if (!stopped) {   // cnmf.m:236-251 of the last iteration: the cost-only form
         TRY(s_map(false, true));
-        TRY(cost_of_pass(p->maxiter - 1));
+        TRY(cost_of_pass(c.maxiter - 1));
     }
-    NMFX_HIP(hipMemcpy(r->cost, dcost.p, (size_t)it * 8, hipMemcpyDeviceToHost));
-    r->cost_len = r->iters_run = it;
-    clock.end(&IoStats::iterate_s);
-    TRY(egress_master(st, W64, W, p->dtype, r->W, mKT));
-    NMFX_HIP(hipStreamSynchronize(st));
-    TRY(egress_master(st, H64, H, p->dtype, r->H, Kn));
-    NMFX_HIP(hipStreamSynchronize(st));
-    clock.end(&IoStats::egress_s);
+    *iters_run = it;
     return NMFX_OK;
 }
 
-}  // namespace
 }  // namespace nmfx
 
 extern "C" nmfx_status nmfx_wcnmf(const nmfx_problem *p, const void *M, nmfx_result *r) { return nmfx::run_wcnmf(p, M, r); }

@@ -43,29 +43,11 @@
 #include "api_common.h"
 #include "dev_reduce.h"
 #include "gemm_common.h"
+#include "weighted_constants.h"
 #include "wnmf_pass.h"
 
 namespace nmfx {
 namespace {
-
-// the constant operands, from the views: `lead` contiguous elements per line, `lines` lines.  MV (or NULL) <- on ? w*v : 0;  Bf (or NULL) <- on ? w : 0.
-// V is read only where M is on (and only when MV is asked for).
-template <class MT>
-__global__ __launch_bounds__(256) void wnmf_dev_prepare(const float *V, long ldv, const MT *M, long ldm, float *MV, float *Bf, long lead, long lines) {
-    const long count = lead * lines;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < count; e += (long)gridDim.x * 256) {
-        const long c = e % lead, l = e / lead;
-        const MT mv = M[c + ldm * l];
-        const bool on = Weight<MT>::on(mv);
-        const float w = Weight<MT>::value(mv);
-        if (MV) {
-            float a = 0.0f;
-            if (on) a = w * V[c + ldv * l];
-            MV[e] = a;
-        }
-        if (Bf) Bf[e] = on ? w : 0.0f;
-    }
-}
 
 template <int LAYOUT, class MT>
 nmfx_status map_launch(int map, hipStream_t st, const WMapDevArgs &g, bool store, bool cost) {
@@ -161,12 +143,7 @@ WnmfWork::WnmfWork(void *base, long m, long n, int K, int map, int m_kind, int m
 nmfx_status wnmf_constants(hipStream_t st, const WnmfCall &c, const WnmfWork &wk) {
     const long lead = c.layout == 0 ? c.m : c.n, lines = c.layout == 0 ? c.n : c.m;   // the contiguous extent, and the one the leading dimension steps over
     float *MV = c.map == WM_EUC ? wk.A : nullptr, *Bf = (c.map == WM_KL && wnmf_own_b(c.map, c.m_kind)) ? wk.B : nullptr;
-    if (!MV && !Bf) return NMFX_OK;
-    const dim3 grid(grid1(lead * lines));
-    if (c.m_kind) hipLaunchKernelGGL((wnmf_dev_prepare<unsigned char>), grid, dim3(256), 0, st, c.V, c.ldv, static_cast<const unsigned char *>(c.M), c.ldm, MV, Bf, lead, lines);
-    else hipLaunchKernelGGL((wnmf_dev_prepare<float>), grid, dim3(256), 0, st, c.V, c.ldv, static_cast<const float *>(c.M), c.ldm, MV, Bf, lead, lines);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
+    return weighted_constants(st, c.V, c.ldv, c.M, c.ldm, c.m_kind, MV, Bf, lead, lines);   // (weighted_constants.h)
 }
 
 nmfx_status wnmf_iterate(hipStream_t st, const WnmfCall &c, const WnmfWork &wk, int *iters_run) {

@@ -2,46 +2,13 @@
 // the caller's stream out of ONE work buffer the caller allocated.  The entry is three steps: the argument checks, the ingest of the float64 inits and of the
 // lambda / fixed vectors, and the driver (wnmf_constants, wnmf_iterate) on the caller's V and M as they are -- views with a leading dimension in either
 // layout, M float32 weights or a byte mask -- followed by the closing copies (column-major) or transposes (row-major) into the caller's outputs.
-// The per-component lambda and fixed vectors reach the device inside kernel arguments (wnmf_dev_vectors, 256 components per launch): no host buffer is read
+// The per-component lambda and fixed vectors reach the device inside kernel arguments (dev_vectors of weighted_dev.h, 256 components per launch): no host buffer is read
 // after the call returns, and no copy waits for the stream.  With the stop rule off nothing here waits for the device, allocates or frees.
 #include "api_common.h"
+#include "weighted_dev.h"
 
 namespace nmfx {
 namespace {
-
-constexpr int VEC_CHUNK = 256;
-struct VecChunk {
-    float lw[VEC_CHUNK], lh[VEC_CHUNK];
-    uint8_t fw[VEC_CHUNK], fh[VEC_CHUNK];
-    int k0, count;
-};
-__global__ __launch_bounds__(VEC_CHUNK) void wnmf_dev_vectors(const VecChunk c, float *lamW, float *lamH, uint8_t *fixW, uint8_t *fixH) {
-    const int q = threadIdx.x;
-    if (q >= c.count) return;
-    lamW[c.k0 + q] = c.lw[q]; lamH[c.k0 + q] = c.lh[q];
-    fixW[c.k0 + q] = c.fw[q]; fixH[c.k0 + q] = c.fh[q];
-}
-
-// float64 inits (the library's layout) -> the masters and their fp32 images
-__global__ __launch_bounds__(256) void wnmf_dev_ingest(const double *in, double *d64, float *d32, long count) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < count; e += (long)gridDim.x * 256) {
-        const double x = in[e];
-        d64[e] = x;
-        d32[e] = (float)x;
-    }
-}
-
-// An upper bound of gemm_scratch_bytes(M, N, Kc) that never falls when M, N or Kc grows (the exact figure does, where the tile shape or the slab count
-// steps): gemm_auto takes the slab count from the shape alone as long as the scratch holds it, so a larger scratch changes no result.  The pipelined
-// kernel's slabs are at most 256, at most a quarter of the 32-wide k tiles, and at most ceil(512 / tiles) with tiles >= M*N / 128^2, which bounds
-// M*N*slabs by M*N + 512 * 128^2; the tiny-product kernel's are at most 64 and ceil(Kc / 32), on outputs of at most 65536 elements.
-size_t gemm_scratch_bound(long M, long N, long Kc) {
-    const size_t mn = (size_t)M * N;
-    const long kt = (Kc + 31) / 32;
-    const size_t pipe = std::min(4 * mn * (size_t)std::min<long>(std::max<long>(kt / 4, 1), 256), 4 * mn + ((size_t)1 << 25));
-    const size_t tiny = 4 * std::min<size_t>(mn, 65536) * (size_t)std::min<long>(kt, 64);
-    return std::max(pipe, tiny);
-}
 
 size_t scratch_bound(long m, long n, int K) { return std::max(gemm_scratch_bound(m, K, n), gemm_scratch_bound(K, n, m)); }
 
@@ -93,30 +60,15 @@ extern "C" nmfx_status nmfx_wnmf_dev(void *stream, int64_t m, int64_t n, int32_t
     WnmfCall c{};
     c.m = m; c.n = n; c.K = K; c.map = map;
     c.V = V_dev; c.M = M_dev; c.ldv = ldv; c.ldm = ldm; c.layout = layout; c.m_kind = m_kind;
-    c.all_wf = c.all_hf = true;
-    for (int k = 0; k < K; ++k) {
-        c.all_wf = c.all_wf && fixW && fixW[k]; c.all_hf = c.all_hf && fixH && fixH[k];
-        c.any_lw = c.any_lw || (lamW && lamW[k] != 0.0f); c.any_lh = c.any_lh || (lamH && lamH[k] != 0.0f);
-    }
+    vector_summaries(c, K, lamW, lamH, fixW, fixH);
     c.maxiter = maxiter; c.tolerance = tolerance;
     DeviceGuard dg_;
     TRY(check_device(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t mK = (size_t)m * K, Kn = (size_t)K * n;
-    for (int k0 = 0; k0 < K; k0 += VEC_CHUNK) {
-        VecChunk v;
-        v.k0 = k0; v.count = std::min(VEC_CHUNK, K - k0);
-        for (int q = 0; q < VEC_CHUNK; ++q) {
-            const bool in = q < v.count;
-            v.lw[q] = in && lamW ? lamW[k0 + q] : 0.0f; v.lh[q] = in && lamH ? lamH[k0 + q] : 0.0f;
-            v.fw[q] = in && fixW ? fixW[k0 + q] != 0 : 0; v.fh[q] = in && fixH ? fixH[k0 + q] != 0 : 0;
-        }
-        hipLaunchKernelGGL(wnmf_dev_vectors, dim3(1), dim3(VEC_CHUNK), 0, st, v, wk.lam, wk.lam + K, wk.fix, wk.fix + K);
-        NMFX_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(wnmf_dev_ingest, dim3(grid1((long)mK)), dim3(256), 0, st, W_init_dev, wk.W64, wk.W, (long)mK);
-    hipLaunchKernelGGL(wnmf_dev_ingest, dim3(grid1((long)Kn)), dim3(256), 0, st, H_init_dev, wk.H64, wk.H, (long)Kn);
-    NMFX_HIP(hipGetLastError());
+    TRY(dev_vectors(st, K, lamW, lamH, fixW, fixH, wk.lam, wk.fix));
+    TRY(dev_ingest(st, W_init_dev, wk.W64, wk.W, mK));
+    TRY(dev_ingest(st, H_init_dev, wk.H64, wk.H, Kn));
 
     int it = 0;
     TRY(wnmf_constants(st, c, wk));

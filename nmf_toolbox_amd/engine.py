@@ -10,7 +10,7 @@ of the packed W-step partials [N | P] (KL: [N | rowsum(H)]).  Everything after t
 computed redundantly and identically on every rank, so W stays bit-identical across ranks.
 
 Single fused passes on torch tensors, at the end of this file: softmask (nmfx_softmask_dev), impute and holdout (nmfx_impute_dev); and the weighted fit
-between them, wnmf (nmfx_wnmf_dev).
+between them, wnmf (nmfx_wnmf_dev) and wcnmf (nmfx_wcnmf_dev).
 """
 from __future__ import annotations
 
@@ -801,9 +801,10 @@ def holdout(V, M, W, H, config=None):
     return _impute_dev("engine.holdout", V, M, W, H, config, True)
 
 
-def _wnmf_inits(fn, cfg, Ks, m, n):
-    """W_init / H_init of engine.wnmf -> (validated config, [W_i], [H_i], is_W_cell, is_H_cell): entries given as numpy arrays or torch tensors (any device,
-    any strides) stay what they are, missing ones are the float64 arrays toolbox.wnmf draws for the same seed / rng (toolbox._validate_shape: H first, then W)"""
+def _wnmf_inits(fn, cfg, Ks, m, n, T=None):
+    """W_init / H_init of engine.wnmf (T None) and engine.wcnmf (T the context length) -> (validated config, [W_i], [H_i], is_W_cell, is_H_cell): entries
+    given as numpy arrays or torch tensors (any device, any strides) stay what they are, missing ones are the float64 arrays the host call of the same name
+    draws for the same seed / rng (toolbox._validate_shape: H first, then W).  With T, every W_i comes back m x K_i x T (m x K_i is accepted when T == 1)."""
     import torch
     from . import toolbox as TB
 
@@ -827,37 +828,45 @@ def _wnmf_inits(fn, cfg, Ks, m, n):
             hold = [np.zeros((1, 1)) for _ in ent]
             cfg2[name] = hold if cell else hold[0]
     try:
-        cfgv, Wl, Hl, is_W_cell, is_H_cell = TB._validate_shape((m, n), Ks, 1, cfg2, False)
+        cfgv, Wl, Hl, is_W_cell, is_H_cell = TB._validate_shape((m, n), Ks, 1 if T is None else T, cfg2, T is not None)
     except ValueError as e:
         raise ValueError("%s: %s" % (fn, e)) from None
     real = _real_entry(fn)
     Wl = [real(a, "W_init") for a in given["W_init"]] if given["W_init"] is not None else Wl
     Hl = [real(a, "H_init") for a in given["H_init"]] if given["H_init"] is not None else Hl
     for s, K in enumerate(Ks):
-        if tuple(Wl[s].shape) != (m, K):
+        if T == 1 and tuple(Wl[s].shape) == (m, K):
+            Wl[s] = Wl[s].reshape(m, K, 1)
+        if T is not None and tuple(Wl[s].shape) != (m, K, T):
+            raise ValueError("%s: W_init{%d} must be %d-by-%d-by-%d; got %r" % (fn, s + 1, m, K, T, tuple(Wl[s].shape)))
+        if T is None and tuple(Wl[s].shape) != (m, K):
             raise ValueError("%s: W_init{%d} must be %d-by-%d; got %r" % (fn, s + 1, m, K, tuple(Wl[s].shape)))
         if tuple(Hl[s].shape) != (K, n):
             raise ValueError("%s: H_init{%d} must be %d-by-%d; got %r" % (fn, s + 1, K, n, tuple(Hl[s].shape)))
     return cfgv, Wl, Hl, is_W_cell, is_H_cell
 
 
-def _wnmf_prepare(V, M, num_basis_elems, config):
-    """every check of engine.wnmf and everything the C call is handed that does not need the device, as a dict; nothing here loads the library"""
+_PLAIN = object()   # context_len of the call that has none (engine.wnmf); None is a value engine.wcnmf refuses
+
+
+def _wnmf_prepare(V, M, num_basis_elems, config, context_len=_PLAIN, fn="engine.wnmf"):
+    """every check of engine.wnmf (and, with context_len and its name, of engine.wcnmf) and everything the C call is handed that does not need the device,
+    as a dict; nothing here loads the library"""
     import torch
     from . import toolbox as TB
-    fn = "engine.wnmf"
     cfg = config if config else {}
     div = TB._weighted_config(fn, cfg)
     check = _nmfx_check(fn, cfg)
     m, n = _vm_shape(fn, V, M, False)
     layout, ldv, ldm, m_kind = _vm_view(fn, V, M)
+    T = None if context_len is _PLAIN else TB._context_len(fn, context_len, n)
     try:
         Ks = [int(k) for k in (num_basis_elems if TB._is_cell(num_basis_elems) else [num_basis_elems])]
     except (TypeError, ValueError):
         raise ValueError("%s: num_basis_elems must be a positive integer or a list of them; got %r" % (fn, num_basis_elems)) from None
     if not Ks or min(Ks) < 1:
         raise ValueError("%s: num_basis_elems must be a positive integer or a list of them; got %r" % (fn, num_basis_elems))
-    cfgv, Wl, Hl, is_W_cell, is_H_cell = _wnmf_inits(fn, cfg, Ks, m, n)
+    cfgv, Wl, Hl, is_W_cell, is_H_cell = _wnmf_inits(fn, cfg, Ks, m, n, T)
     # the values, where they live: torch inits and a float32 M by flags read back together (the one synchronisation nmfx_check = False avoids), numpy inits
     # on the host; inits travel as float32, as in the host call with a float32 V
     flags = {}
@@ -867,7 +876,7 @@ def _wnmf_prepare(V, M, num_basis_elems, config):
     _raise_flags(flags, messages)
     rep = lambda key, dt: np.ascontiguousarray(np.repeat(np.asarray(cfgv[key]).astype(dt), Ks))
     maxiter = int(cfgv["maxiter"])
-    return dict(fn=fn, m=m, n=n, Ks=Ks, K=int(sum(Ks)), div=TB._DIV_WNMF[div], layout=layout, ldv=ldv, ldm=ldm, m_kind=m_kind,
+    return dict(fn=fn, m=m, n=n, Ks=Ks, K=int(sum(Ks)), T=T, div=TB._DIV_WNMF[div], layout=layout, ldv=ldv, ldm=ldm, m_kind=m_kind,
                 W32=W32, H32=H32, is_W_cell=is_W_cell, is_H_cell=is_H_cell, maxiter=maxiter,
                 tolerance=-1.0 if cfgv.get("nmfx_disable_stop", False) else float(cfgv["tolerance"]),
                 lamW=rep("W_sparsity", np.float32), lamH=rep("H_sparsity", np.float32), fixW=rep("W_fixed", np.uint8), fixH=rep("H_fixed", np.uint8))
@@ -899,42 +908,84 @@ def wnmf(V, M, num_basis_elems, config=None):
     Refused: what toolbox.wnmf refuses ('ab' and unknown divergences, nmfx_gpus, nmfx_multi_backend, nmfx_precision='float64', M of another shape); a V
     or M that is not a torch tensor; a V that is not 2-D, is empty or is not float32; M of another dtype, device or layout class; no unit stride, or
     overlap; lazy conj / neg views.  A CPU tensor that passes every check ends in NmfxError(NMFX_ERR_NO_DEVICE): there is no CPU fallback."""
+    return _weighted_fit(_wnmf_prepare(V, M, num_basis_elems, config), V, M)
+
+
+def _weighted_fit(a, V, M):
+    """the device half of engine.wnmf and engine.wcnmf (a: what _wnmf_prepare returned; a["T"] is None for wnmf): the float64 inits in the library's
+    layout, the work buffer, the one call into nmfx_wnmf_dev / nmfx_wcnmf_dev, and the factors as views of what it wrote"""
     import torch
-    a = _wnmf_prepare(V, M, num_basis_elems, config)
-    fn, m, n, K, Ks, layout = a["fn"], a["m"], a["n"], a["K"], a["Ks"], a["layout"]
+    fn, m, n, K, Ks, T, layout = a["fn"], a["m"], a["n"], a["K"], a["Ks"], a["T"], a["layout"]
     if not V.is_cuda:
         raise _lib.NmfxError(_lib.NMFX_ERR_NO_DEVICE, "%s needs a CUDA/HIP tensor V: there is no CPU fallback" % fn)
     dev = V.device
-    # the float64 inits in the library's layout, W[i + m*k] = a contiguous (K, m) tensor and H[k + K*j] = a contiguous (n, K) one, from the fp32 entries
-    W0 = torch.cat([w.to(dev) for w in a["W32"]], dim=1).t().contiguous().to(torch.float64)
+    conv = T is not None
+    KT = K * T if conv else K
+    # the float64 inits in the library's layout, from the fp32 entries: W[i + m*k] = a contiguous (K, m) tensor, or the flat image W[i + m*(t*K + k)] = a
+    # contiguous (T, K, m) one; H[k + K*j] = a contiguous (n, K) one
+    Wc = torch.cat([w.to(dev) for w in a["W32"]], dim=1)
+    W0 = (Wc.permute(2, 1, 0) if conv else Wc.t()).contiguous().to(torch.float64)
     H0 = torch.cat([h.to(dev) for h in a["H32"]], dim=0).t().contiguous().to(torch.float64)
     lib = _lib.load()
+    query, entry = (lib.nmfx_wcnmf_dev_work_bytes, lib.nmfx_wcnmf_dev) if conv else (lib.nmfx_wnmf_dev_work_bytes, lib.nmfx_wnmf_dev)
+    shape = (m, n, K, T) if conv else (m, n, K)
     need = C.c_size_t()
-    _lib.check(lib.nmfx_wnmf_dev_work_bytes(m, n, K, a["div"], a["m_kind"], a["maxiter"], C.byref(need)))
+    _lib.check(query(*shape, a["div"], a["m_kind"], a["maxiter"], C.byref(need)))
     work = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    # what the C entry writes, and the factors as views of it without a copy: row-major W (m, KT) = (m, T, K), column-major its transpose (KT, m) = (T, K, m)
+    # (cutW / cutH: the components lo .. hi - 1 of what was written, `copy`: as a fresh contiguous allocation, in the natural shape)
+    own = lambda x, copy: x.contiguous() if copy else x
     if layout == 1:
-        Wt, Ht = torch.empty((m, K), dtype=torch.float32, device=dev), torch.empty((K, n), dtype=torch.float32, device=dev)
-        W, H = Wt, Ht
+        Wt, Ht = torch.empty((m, KT), dtype=torch.float32, device=dev), torch.empty((K, n), dtype=torch.float32, device=dev)
+        cutW = (lambda lo, hi, copy: own(Wt.view(m, T, K)[:, :, lo:hi], copy).permute(0, 2, 1)) if conv else (lambda lo, hi, copy: own(Wt[:, lo:hi], copy))
+        cutH = lambda lo, hi, copy: own(Ht[lo:hi], copy)
     else:
-        Wt, Ht = torch.empty((K, m), dtype=torch.float32, device=dev), torch.empty((n, K), dtype=torch.float32, device=dev)
-        W, H = Wt.t(), Ht.t()
+        Wt, Ht = torch.empty((KT, m), dtype=torch.float32, device=dev), torch.empty((n, K), dtype=torch.float32, device=dev)
+        cutW = (lambda lo, hi, copy: own(Wt.view(T, K, m)[:, lo:hi], copy).permute(2, 1, 0)) if conv else (lambda lo, hi, copy: own(Wt[lo:hi], copy).t())
+        cutH = lambda lo, hi, copy: own(Ht[:, lo:hi], copy).t()
     cost = torch.empty(a["maxiter"], dtype=torch.float64, device=dev)
     iters = C.c_int32(0)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     index = dev.index if dev.index is not None else torch.cuda.current_device()
     ptr = lambda arr: arr.ctypes.data_as(C.c_void_p)
-    _lib.check(lib.nmfx_wnmf_dev(stream, m, n, K, a["div"], layout, C.c_void_p(V.data_ptr()), a["ldv"], C.c_void_p(M.data_ptr()), a["ldm"], a["m_kind"],
-                                 ptr(a["lamW"]), ptr(a["lamH"]), ptr(a["fixW"]), ptr(a["fixH"]), C.c_void_p(W0.data_ptr()), C.c_void_p(H0.data_ptr()),
-                                 a["maxiter"], a["tolerance"], C.c_void_p(work.data_ptr()), need.value, C.c_void_p(Wt.data_ptr()), C.c_void_p(Ht.data_ptr()),
-                                 C.c_void_p(cost.data_ptr()), C.byref(iters), index))
+    _lib.check(entry(stream, *shape, a["div"], layout, C.c_void_p(V.data_ptr()), a["ldv"], C.c_void_p(M.data_ptr()), a["ldm"], a["m_kind"],
+                     ptr(a["lamW"]), ptr(a["lamH"]), ptr(a["fixW"]), ptr(a["fixH"]), C.c_void_p(W0.data_ptr()), C.c_void_p(H0.data_ptr()),
+                     a["maxiter"], a["tolerance"], C.c_void_p(work.data_ptr()), need.value, C.c_void_p(Wt.data_ptr()), C.c_void_p(Ht.data_ptr()),
+                     C.c_void_p(cost.data_ptr()), C.byref(iters), index))
     # (W0, H0 and work go back to torch's allocator when this frame ends: it reuses them in stream order, behind the kernels launched above)
     cost = cost[: iters.value]
     if len(Ks) > 1:      # one fresh contiguous tensor per source, in the layout class
-        offs = np.concatenate([[0], np.cumsum(Ks)])
-        cut = (lambda t, lo, hi, rows: (t[lo:hi] if rows else t[:, lo:hi]).contiguous()) if layout == 1 else \
-              (lambda t, lo, hi, rows: (t.t()[:, lo:hi] if rows else t.t()[lo:hi]).contiguous().t())
-        Wl = [cut(W, int(offs[s]), int(offs[s + 1]), False) for s in range(len(Ks))]
-        Hl = [cut(H, int(offs[s]), int(offs[s + 1]), True) for s in range(len(Ks))]
+        offs = [int(o) for o in np.concatenate([[0], np.cumsum(Ks)])]
+        Wl = [cutW(offs[s], offs[s + 1], True) for s in range(len(Ks))]
+        Hl = [cutH(offs[s], offs[s + 1], True) for s in range(len(Ks))]
     else:
-        Wl, Hl = [W], [H]
+        Wl, Hl = [cutW(0, K, False)], [cutH(0, K, False)]
+    if T == 1:           # rand(m,K,1) is a matrix in MATLAB
+        Wl = [w[:, :, 0] for w in Wl]
     return (Wl if a["is_W_cell"] else Wl[0]), (Hl if a["is_H_cell"] else Hl[0]), cost
+
+
+def wcnmf(V, M, num_basis_elems, context_len, config=None):
+    """W, H, cost = engine.wcnmf(V, M, num_basis_elems, context_len, config): toolbox.wcnmf on data that lives on the GPU, on torch's current stream of
+    V's device; the factors and the cost stay there.  Same update equations (csrc/wcnmf.hip), the same arithmetic and the same config keys.
+
+    V and M are engine.wnmf's, by the same rules: V a 2-D float32 tensor, row-major (stride (ld, 1), ld >= n: what torch.stft returns per batch entry) or
+    column-major (stride (1, ld), ld >= m), slices welcome, passed by pointer, never copied, never written and never looked at where M == 0; M of V's
+    shape on V's device in V's layout class with its own leading dimension, float32 weights (>= 0 and finite) or torch.bool / torch.uint8.
+    num_basis_elems, context_len and config are toolbox.wcnmf's: several sources as lists; 1 <= context_len <= 64 and n >= context_len - 1; divergence
+    'euclidean', 'kl' / 'kl_divergence', 'is' / 'is_divergence'; W_sparsity, H_sparsity, W_fixed, H_fixed, maxiter, tolerance, nmfx_disable_stop, seed /
+    rng, W_init (m x K x T; m x K accepted when context_len == 1), H_init.  Entries of W_init / H_init are numpy arrays or torch tensors on any device
+    with any strides; missing ones are the arrays toolbox.wcnmf draws for the same seed.  Inits travel as float32, as in the host call with a float32 V.
+    config['nmfx_check'] is engine.wnmf's.
+
+    Returns what toolbox.wcnmf returns for a float32 V, as tensors on V's device: W float32 m x K x T (m x K when context_len == 1), a view without a
+    copy of what the C entry wrote -- column-major V: a permute(2, 1, 0) view of the contiguous (T, K, m) image, row-major V: a view of the contiguous
+    (m, T, K) array --, H (K x n) in V's layout class as from engine.wnmf, both the fp32 images of the float64 masters; lists per source, each a fresh
+    contiguous cut, when num_basis_elems is a list; cost float64, trimmed to the iterations run.  engine.holdout, engine.impute and engine.softmask take
+    W and H as returned, with the same V: nothing goes through the host.
+    With nmfx_disable_stop=True, nmfx_check=False and inits that are already on V's device the call waits for nothing and all device memory comes from
+    torch: one work buffer of nmfx_wcnmf_dev_work_bytes (4*m*n bytes for kl with float32 weights, 8*m*n otherwise, plus K*T*(20*m + 8*n), O((m + n)*K +
+    maxiter) and the GEMM scratch).
+    Refused, naming engine.wcnmf, before the library is loaded: what toolbox.wcnmf refuses and what engine.wnmf refuses about V and M.  A CPU tensor that
+    passes every check ends in NmfxError(NMFX_ERR_NO_DEVICE): there is no CPU fallback."""
+    return _weighted_fit(_wnmf_prepare(V, M, num_basis_elems, config, context_len, "engine.wcnmf"), V, M)

@@ -343,6 +343,19 @@ def wnmf(V, M, num_basis_elems, config=None, device=0):
 WCNMF_MAX_CONTEXT = 64
 
 
+def _context_len(fn, context_len, n):
+    """context_len of wcnmf and engine.wcnmf -> T: an integer from 1 to WCNMF_MAX_CONTEXT, and n >= T - 1 columns"""
+    try:
+        T = int(context_len)
+    except (TypeError, ValueError):
+        raise ValueError("%s: context_len must be an integer from 1 to %d; got %r" % (fn, WCNMF_MAX_CONTEXT, context_len)) from None
+    if T != context_len or T < 1 or T > WCNMF_MAX_CONTEXT:
+        raise ValueError("%s: context_len must be an integer from 1 to %d; got %r" % (fn, WCNMF_MAX_CONTEXT, context_len))
+    if n < T - 1:
+        raise ValueError("%s: V has %d columns, fewer than context_len - 1 = %d" % (fn, n, T - 1))
+    return T
+
+
 def wcnmf(V, M, num_basis_elems, context_len, config=None, device=0):
     """W, H, cost = wcnmf(V, M, num_basis_elems, context_len, config): weighted convolutive NMF -- cnmf (cnmf.m:1) with every element of the data fit
     weighted by M >= 0, for missing or unreliable entries of V.  With T = context_len, S = sum_t W(:,:,t) * rshift_t(H) and wnmf's table of A, B and d(V, S):
@@ -361,14 +374,7 @@ def wcnmf(V, M, num_basis_elems, context_len, config=None, device=0):
     fp32 device arithmetic with float64 master copies of W and H: nmfx_gpus, nmfx_multi_backend and nmfx_precision='float64' are refused, nmfx_path is
     ignored (there is one path)."""
     V, Mf, div = _weighted_inputs("wcnmf", V, M, config)
-    try:
-        T = int(context_len)
-    except (TypeError, ValueError):
-        raise ValueError("wcnmf: context_len must be an integer from 1 to %d; got %r" % (WCNMF_MAX_CONTEXT, context_len)) from None
-    if T != context_len or T < 1 or T > WCNMF_MAX_CONTEXT:
-        raise ValueError("wcnmf: context_len must be an integer from 1 to %d; got %r" % (WCNMF_MAX_CONTEXT, context_len))
-    if V.shape[1] < T - 1:
-        raise ValueError("wcnmf: V has %d columns, fewer than context_len - 1 = %d" % (V.shape[1], T - 1))
+    T = _context_len("wcnmf", context_len, V.shape[1])
     Ks = [int(k) for k in (num_basis_elems if _is_cell(num_basis_elems) else [num_basis_elems])]
     cfg, W, H, is_W_cell, is_H_cell = _validate(V, Ks, T, config, True)                            # cnmf.m:131
     lib = _lib.load()

@@ -76,7 +76,7 @@ def main():
     lines = []
     if a.stats:
         for r in from_stats(a.stats)[:30]:
-            t = re.search(r"w(c?)map_kernel<\d+, (true|false), (true|false)>", r["name"])       # <MAP, STORE, COST>
+            t = re.search(r"w(c?)map_kernel<\d+, (true|false), (true|false)[,>]", r["name"])    # <MAP, STORE, COST(, LAYOUT, MT)>
             if t:
                 b = M_ * N_ * (8 + (4 if t.group(2) == "true" else 0))
                 r.update(element_bytes=b, element_us_at_3TBps=b / HBM_REFERENCE * 1e6, element_TBps=b / (r["mean_us"] * 1e-6) / 1e12,
