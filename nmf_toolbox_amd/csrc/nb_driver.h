@@ -1,46 +1,23 @@
 // The one host driver behind nmfx_nmf_batch, nmfx_cnmf_batch, nmfx_wnmf_batch and nmfx_wcnmf_batch.  Host code only; included
-// after nb_pass.h by the four batch translation units, each of which keeps its own kernels and hands nb_drive a VARIANT: a small struct that says which pass
-// kernel it runs and launches the three kernels that are its own.
+// after nb_pass.h and nb_update.h by the four batch translation units, each of which calls nb_drive<CONV, WGT> with its name:
+//     CONV: the convolutive refusals, W of m*K*T doubles per problem, the Q buffer and nb_hupdate after the H-step pass
+//     WGT:  M is required and uploaded beside V, two slab sets for kl too, no colsum(W) operand of the pass
+// They are the arguments of nb_run_pass<CONV, WGT> and of the update kernels (nb_update.h), which take one argument struct, filled here once.
 //
-//     struct Variant {
-//         static constexpr bool CONV, WGT;        // the nb_run_pass<CONV, WGT> arguments.  CONV: the convolutive refusals, W of m*K*T doubles per problem, the
-//                                                 // Q buffer and the H update after the H-step pass.  WGT: M is required and uploaded beside V, two slab sets
-//                                                 // for kl too, no colsum(W) operand of the pass
-//         static constexpr const char *NAME;      // the call's name in every message
-//         <its argument structs>                  // filled once by init, passed to its kernels as they are
-//         nmfx_status init(hipStream_t, const NbState &);   // fills them and launches the normalisation of the W_init (nb_wnorm / wb_wnorm / cb_winit / wcb_winit)
-//         nmfx_status wupdate(hipStream_t);                 // the W update from the slabs of the W-step pass
-//         nmfx_status hupdate(hipStream_t);                 // CONV only: the H update from Q (and P) of the H-step pass
-//     };
-//
-// Everything else is here once: the argument checks in their order, the work tables, the buffers, the staging in and out, and the launch sequence.
+// Everything is here once: the argument checks in their order, the work tables, the buffers, the staging in and out, and the launch sequence.
 //
 // One iteration, plain launches on one stream for the whole batch:
-//     nb_pass<W step>  ->  nb_decide (per problem: cost(t-1) summed in item order, + the L1 terms, the stop rule, done[b])  ->  wupdate (per problem and column:
-//     chunk slabs summed in chunk order, the diag terms, eps guard, the norm, both copies of W)  ->  nb_pass<H step>  [-> hupdate]
+//     nb_pass<W step>  ->  nb_decide (per problem: cost(t-1) summed in item order, + the L1 terms, the stop rule, done[b])  ->  nb_wupdate (per problem and column:
+//     chunk slabs summed in chunk order, the diag terms, eps guard, the norm, both copies of W)  ->  nb_pass<H step>  [CONV: -> nb_hupdate]
 // With two accumulator sets at KP = 256 (euclidean; WGT: kl too) each pass is two launches (nb_pass.h, WHICH).  Work items of a problem with done[b] != 0
 // return at once: its W_b, H_b and cost vector stay as they were when its stop rule fired.  After the last iteration one cost-only W-step pass and one
 // nb_decide close the cost vectors.  The host reads done[] every 16 iterations (only when the stop rule is on) to end early.
 #pragma once
 #include "nb_pass.h"
+#include "nb_update.h"
 
 namespace nmfx {
 namespace {
-
-// what the driver has set up when it calls Variant::init: device pointers and sizes
-struct NbState {
-    const NbProb *prob;
-    const int *done;
-    const int *htab;        // item -> problem of the H step, 64 columns per item
-    int hitems;
-    const double *slab;
-    double *Wm, *WT, *Hm;   // WT: the pass operand (CONV: WC)
-    double *cw;             // K*B doubles (WGT and CONV: K*T*B, per slice; WGT alone: none)
-    const double *Q, *P;    // CONV: K*T x N
-    long m, cols;           // cols = K*B, one workgroup each in init and wupdate
-    int K, T, KP, euc;
-    double lamW, lamH;
-};
 
 // a plain launch with a workgroup per item
 template <class... P, class... A>
@@ -50,10 +27,8 @@ nmfx_status nb_each(void (*kernel)(P...), long count, hipStream_t st, const A &.
     return NMFX_OK;
 }
 
-template <class Variant>
-nmfx_status nb_drive(const nmfx_problem *p, const void *M, int32_t batch, const int64_t *off, nmfx_result *r, int32_t *cost_len) {
-    constexpr bool CONV = Variant::CONV, WGT = Variant::WGT;
-    constexpr const char *fn = Variant::NAME;
+template <bool CONV, bool WGT>
+nmfx_status nb_drive(const char *fn, const nmfx_problem *p, const void *M, int32_t batch, const int64_t *off, nmfx_result *r, int32_t *cost_len) {
     TRY(validate_problem(p, r, false, true));
     if (WGT && !M) { set_error("%s: the weights M are required", fn); return NMFX_ERR_INVALID; }
     if (!off || !cost_len) { set_error("%s: col_offsets and cost_len are required", fn); return NMFX_ERR_INVALID; }
@@ -135,12 +110,11 @@ nmfx_status nb_drive(const nmfx_problem *p, const void *M, int32_t batch, const 
     NMFX_HIP(hipStreamSynchronize(st));   // (the caller's pageable buffers and the host tables have been read)
     clock.end(&IoStats::ingest_s);
 
-    NbState s{};
+    NbUpdate s{};
     s.prob = dprob.as<NbProb>(); s.done = ddone.as<int>(); s.htab = dhtab.as<int>(); s.hitems = (int)hi; s.slab = slab.as<double>();
     s.Wm = Wm.as<double>(); s.WT = WT.as<double>(); s.Hm = Hm.as<double>(); s.cw = cw.as<double>(); s.Q = Qb.as<double>(); s.P = Pb.as<double>();
     s.m = m; s.cols = (long)K * B; s.K = K; s.T = T; s.KP = KP; s.euc = div == NB_EUC; s.lamW = lamW; s.lamH = lamH;
-    Variant v;
-    TRY(v.init(st, s));   // nmf.m:130-134, cnmf.m:157-166
+    TRY(nb_each(nb_winit<CONV, WGT>, s.cols, st, s));   // nmf.m:130-134, cnmf.m:157-166
     NbPass wp{};
     wp.prob = dprob.as<NbProb>(); wp.tab = dwtab.as<int>(); wp.items = (int)wi; wp.done = ddone.as<int>(); wp.V = Vd.as<float>(); wp.m = m; wp.K = KT;
     wp.WT = WT.as<double>(); wp.slab = slab.as<double>(); wp.costpart = cpart.as<double>(); wp.Hm = Hm.as<double>();
@@ -170,10 +144,10 @@ nmfx_status nb_drive(const nmfx_problem *p, const void *M, int32_t batch, const 
                 if (all_done) break;
             }
         }
-        if (!fixW) TRY(v.wupdate(st));
+        if (!fixW) TRY(nb_each(nb_wupdate<CONV, WGT>, s.cols, st, s));
         if (!fixH) {
             TRY((nb_run_pass<CONV, WGT>(st, hp, div, true)));
-            if constexpr (CONV) TRY(v.hupdate(st));
+            if constexpr (CONV) TRY(nb_each(nb_hupdate<WGT>, s.hitems, st, s));
         }
     }
     if (!all_done) {   // nmf.m:203-218, cnmf.m:236-251 of the last iteration, for the problems still running

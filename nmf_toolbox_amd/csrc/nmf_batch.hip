@@ -20,121 +20,11 @@
 // atomic, and so a problem's result is bit-identical wherever it sits in the batch and from run to run.
 //
 // The launch sequence -- four plain launches per iteration on one stream for the whole batch, nb_wupdate between the two passes -- is nb_driver.h's, which
-// holds the host driver this file shares with the other three batch calls; here are the kernels that are nmf_batch's own and its variant of the driver.
-#include "nb_pass.h"
+// holds the host driver this file shares with the other three batch calls; the update kernels are nb_update.h's.  This file instantiates both with
+// CONV = false, WGT = false, and nothing else is here.
+#include "nb_update.h"
 #include "nb_driver.h"
 
-namespace nmfx {
-namespace {
-
-// nmf.m:130-134 for every column of every W_b (fixed or not): unit-L2 columns on the master, the transposed copy, colsum(W) (the KL H-step denominator).
-// A workgroup per (problem, column).  Sum of squares: thread t adds rows t, t + 256, ... in order (fma), then block_sum256
-__global__ __launch_bounds__(256) void nb_wnorm(double *Wm, double *WT, double *cw, long m, int K, long cols) {
-    __shared__ double sh[4];
-    for (long c = blockIdx.x; c < cols; c += gridDim.x) {
-        const long b = c / K;
-        const int k = (int)(c - b * K);
-        double *w = Wm + c * m;
-        double *wt = WT + b * m * K + k;
-        double ss = 0.0;
-        for (long i = threadIdx.x; i < m; i += 256) ss = fma(w[i], w[i], ss);
-        ss = block_sum256(ss, sh);
-        const double sc = 1.0 / sqrt(ss);
-        double cs = 0.0;
-        for (long i = threadIdx.x; i < m; i += 256) {
-            const double y = w[i] * sc;
-            w[i] = y;
-            wt[i * K] = y;
-            cs += y;
-        }
-        cs = block_sum256(cs, sh);
-        if (threadIdx.x == 0) cw[c] = cs;
-    }
-}
-
-struct NbWup {
-    const NbProb *prob;
-    const int *done;
-    const double *slab;
-    double *Wm;
-    double *WT;
-    const double *Hm;
-    double *cw;
-    long m, cols;
-    int K, KP, euc;
-    double lamW;
-};
-// nmf.m:148-153,168-169 for one column of one live problem: N (and P) = the chunk slabs of the W-step pass added in chunk order, in double;
-// neg = N + W.*cs(W.*P), pos = P + W.*cs(W.*N) (the diag(diag(.)) terms are these column sums); KL: P(i, k) = rowsum(H_b)(k), summed here from the master;
-// W .* (neg ./ max(pos + lambda, eps)); unit-L2 column; master, image and colsum(W)
-__global__ __launch_bounds__(256) void nb_wupdate(const NbWup g) {
-    __shared__ double sh[4];
-    const long slabsz = (long)(g.euc ? 2 : 1) * g.KP * NB_T;
-    for (long c = blockIdx.x; c < g.cols; c += gridDim.x) {
-        const long b = c / g.K;
-        const int k = (int)(c - b * g.K);
-        if (g.done[b]) continue;   // (uniform)
-        const NbProb pb = g.prob[b];
-        double *w = g.Wm + c * g.m;
-        double *wt = g.WT + b * g.m * g.K + k;
-        auto slabsum = [&](long i, int which) {
-            const double *p = g.slab + (long)(pb.witem0 + (i / NB_T) * pb.nc) * slabsz + (long)(which * g.KP + k) * NB_T + i % NB_T;
-            double s = 0.0;
-            for (int ch = 0; ch < pb.nc; ++ch) s += p[ch * slabsz];
-            return s;
-        };
-        double pv = 0.0;
-        if (!g.euc) {
-            const double *h = g.Hm + pb.col0 * g.K + k;
-            for (long j = threadIdx.x; j < pb.n; j += 256) pv += h[j * g.K];
-            pv = block_sum256(pv, sh);
-        }
-        double csp = 0.0, csn = 0.0;
-        for (long i = threadIdx.x; i < g.m; i += 256) {
-            const double x = w[i];
-            csp += x * (g.euc ? slabsum(i, 1) : pv);
-            csn += x * slabsum(i, 0);
-        }
-        csp = block_sum256(csp, sh);
-        csn = block_sum256(csn, sh);
-        double ss = 0.0;
-        for (long i = threadIdx.x; i < g.m; i += 256) {
-            const double x = w[i];
-            const double neg = slabsum(i, 0) + x * csp, pos = (g.euc ? slabsum(i, 1) : pv) + x * csn;
-            const double y = x * (neg / fmax(pos + g.lamW, EPS64));
-            w[i] = y;
-            ss += y * y;
-        }
-        ss = block_sum256(ss, sh);
-        const double sc = 1.0 / sqrt(ss);
-        double cs = 0.0;
-        for (long i = threadIdx.x; i < g.m; i += 256) {   // (each thread rescales what it wrote itself)
-            const double y = w[i] * sc;
-            w[i] = y;
-            wt[i * g.K] = y;
-            cs += y;
-        }
-        cs = block_sum256(cs, sh);
-        if (threadIdx.x == 0) g.cw[c] = cs;
-    }
-}
-
-// nb_drive's variant (nb_driver.h)
-struct NmfBatch {
-    static constexpr bool CONV = false, WGT = false;
-    static constexpr const char *NAME = "nmf_batch";
-    NbWup wu{};
-    nmfx_status init(hipStream_t st, const NbState &s) {
-        wu.prob = s.prob; wu.done = s.done; wu.slab = s.slab; wu.Wm = s.Wm; wu.WT = s.WT; wu.Hm = s.Hm;
-        wu.cw = s.cw; wu.m = s.m; wu.cols = s.cols; wu.K = s.K; wu.KP = s.KP; wu.euc = s.euc; wu.lamW = s.lamW;
-        return nb_each(nb_wnorm, s.cols, st, s.Wm, s.WT, s.cw, s.m, s.K, s.cols);
-    }
-    nmfx_status wupdate(hipStream_t st) { return nb_each(nb_wupdate, wu.cols, st, wu); }
-};
-
-}  // namespace
-}  // namespace nmfx
-
 extern "C" nmfx_status nmfx_nmf_batch(const nmfx_problem *p, int32_t batch, const int64_t *col_offsets, nmfx_result *r, int32_t *cost_len) {
-    return nmfx::nb_drive<nmfx::NmfBatch>(p, nullptr, batch, col_offsets, r, cost_len);
+    return nmfx::nb_drive<false, false>("nmf_batch", p, nullptr, batch, col_offsets, r, cost_len);
 }

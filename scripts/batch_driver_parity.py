@@ -1,7 +1,9 @@
 """Two checkouts of this repository, each with its library built, compared on nmf_batch / cnmf_batch / wnmf_batch / wcnmf_batch: does a refactor of the batch
-drivers (csrc/nb_driver.h, toolbox._batch) leave every observable thing as it was?  (profiles/refactor_one_batch_driver.md)
+drivers (csrc/nb_driver.h, toolbox._batch) or of their kernels (csrc/nb_update.h) leave every observable thing as it was?  (profiles/refactor_one_batch_driver.md,
+profiles/refactor_batch_update_kernels.md)
 
-    python scripts/batch_driver_parity.py compare device PARENT RESULT     # no GPU: per kernel symbol of the four batch objects, the instructions and the register / LDS / scratch figures
+    python scripts/batch_driver_parity.py compare device PARENT RESULT     # no GPU: per kernel symbol of the four batch objects, the instructions and the register / LDS / scratch figures;
+                                                                           # a kernel of RENAMED: both sides' figures, and no scratch or spill that the parent does not have
     python scripts/batch_driver_parity.py compare abi    PARENT RESULT     # no GPU: status and nmfx_last_error() text of every refusal of the C entries
     python scripts/batch_driver_parity.py compare python PARENT RESULT     # no GPU: what toolbox.py hands to the library, what it returns, what it refuses
     python scripts/batch_driver_parity.py compare gpu    PARENT RESULT     # one GPU: every returned W, H and cost vector, np.array_equal
@@ -11,6 +13,7 @@ inputs are this checkout's tests/*_batch_inputs.py on both sides.  Exit status 0
 import ctypes as C
 import os
 import pickle
+import re
 import subprocess
 import sys
 import tempfile
@@ -19,6 +22,16 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CALLS = ("nmf_batch", "cnmf_batch", "wnmf_batch", "wcnmf_batch")
+# m, K, n_b, iterations (the convolutive calls: T = 3).  The cases of tests/*_batch_inputs.py have m of 7, 66, 70 and 129; with m > 256 a thread of the update kernels
+# takes a second, ragged trip through its `i += 256` loops, and there the order of the block sums shows in the last bit
+TALL = (300, 5, [65, 9, 130], 10)
+# old update kernel -> the instantiation of csrc/nb_update.h that replaces it, per object file (`compare device`)
+RENAMED = {
+    "nmf_batch": {"nb_wnorm": "nb_winit<false, false>", "nb_wupdate": "nb_wupdate<false, false>"},
+    "cnmf_batch": {"cb_winit": "nb_winit<true, false>", "cb_wupdate": "nb_wupdate<true, false>", "cb_hupdate": "nb_hupdate<false>"},
+    "wnmf_batch": {"wb_wnorm": "nb_winit<false, true>", "wb_wupdate": "nb_wupdate<false, true>"},
+    "wcnmf_batch": {"wcb_winit": "nb_winit<true, true>", "wcb_wupdate": "nb_wupdate<true, true>", "wcb_hupdate": "nb_hupdate<true>"},
+}
 SWITCHES = {"sparse": dict(W_sparsity=0.1, H_sparsity=0.2), "W_fixed": dict(W_fixed=True), "H_fixed": dict(H_fixed=True), "both_fixed": dict(W_fixed=True, H_fixed=True)}
 conv = lambda fn: "cnmf" in fn
 weighted = lambda fn: fn.startswith("w")
@@ -235,6 +248,7 @@ def dump_gpu():
                 for maxiter in (1, 17):
                     run("maxiter %d / %s / %s" % (maxiter, div, kind), I.SWITCH_CASE[:-1], kind, dict(divergence=div, maxiter=maxiter, nmfx_disable_stop=True))
                     run("maxiter %d, stop rule on / %s / %s" % (maxiter, div, kind), I.SWITCH_CASE[:-1], kind, dict(divergence=div, maxiter=maxiter, tolerance=1e-3))
+                run("m300 / %s / %s" % (div, kind), (TALL[0], TALL[1]) + ((3,) if conv(fn) else ()) + (TALL[2],), kind, dict(divergence=div, maxiter=TALL[3], nmfx_disable_stop=True))
                 tol = I.STOP_TOL[div] if isinstance(getattr(I, "STOP_TOL", 0.1), dict) else getattr(I, "STOP_TOL", 0.1)
                 run("stop rule on STOP_CASE / %s / %s" % (div, kind), I.STOP_CASE, kind, dict(divergence=div, maxiter=400, tolerance=tol), planted=True)
     return out
@@ -243,7 +257,6 @@ def dump_gpu():
 # ---- the device code ---------------------------------------------------------------------------------------------------------------------------------------------
 def dump_device(root):
     """kernel symbol -> (resource figures, instruction text) of the gfx950 code objects in the four batch object files of a built checkout"""
-    import re
     from kernel_resources import code_objects, kernels
     out = {}
     for fn in CALLS:
@@ -256,7 +269,7 @@ def dump_device(root):
                 dis = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", "--no-show-raw-insn", t.name], capture_output=True, text=True, check=True).stdout
             for sym, body in re.findall(r"^[0-9a-f]+ <([^>]+)>:\n(.*?)(?=^[0-9a-f]+ <[^>]+>:\n|\Z)", dis, re.M | re.S):
                 if sym in figures:      # (a kernel; the other symbols are the labels inside one, and stay in its text)
-                    out["%s / %s" % (fn, sym)] = (figures[sym], [re.sub(r"\s*//.*", "", line).strip() for line in body.splitlines() if line.strip()])
+                    out["%s / %s" % (fn, sym)] = (figures[sym], [re.sub(r"\s*//.*", "", line).strip() for line in body.splitlines() if line.strip() not in ("", "...")])      # ("...": the zero padding before the next kernel, which may be another one now)
     return out
 
 
@@ -297,18 +310,46 @@ def main(argv):
     if kind == "device":
         sys.path.insert(0, HERE)
         parent, result = dump_device(roots[0]), dump_device(roots[1])
-        differ = [k for k in parent if parent[k] != result.get(k)] + [k for k in result if k not in parent]
+        def mangled(name):
+            """a function's name with its boolean template arguments, as it stands inside its symbol"""
+            base, _, targs = name.partition("<")
+            return "%d%s%sE" % (len(base), base, "I%sE" % "".join("Lb%dE" % (a.strip() == "true") for a in targs[:-1].split(",")) if targs else "")
+        pairs = []      # (parent's key, result's key, old name, new name) of every renamed kernel that both sides have under its two names
+        for fn, names in RENAMED.items():
+            for old, new in names.items():
+                a = [k for k in parent if k.startswith(fn + " / ") and mangled(old) in k]
+                b = [k for k in result if k.startswith(fn + " / ") and mangled(new) in k]
+                if a and b:
+                    pairs.append((a[0], b[0], old, new))
+        for side, col in ((parent, 0), (result, 1)):
+            for k in [p[col] for p in pairs]:
+                side[" renamed " + k] = side.pop(k)
+        differ = [k for k in parent if k[0] != " " and parent[k] != result.get(k)] + [k for k in result if k[0] != " " and k not in parent]
+        if pairs:       # figures side by side; what fails is scratch or a spill that the parent does not have
+            text = lambda k, v: [line.replace(k.split(" / ")[1], "") for line in v[1]]      # (a kernel's own name stands in the targets of its branches)
+            f64 = lambda v: sorted(line.split()[0] for line in v[1] if re.match(r"v_\w*f64|v_div|v_rcp|v_rsq|v_sqrt", line))      # the float64 arithmetic, by mnemonic
+            print("| object | parent | result | VGPRs | SGPRs | LDS | scratch | VGPR spills | SGPR spills | instructions | text | float64 instructions |\n|---|---|---|---|---|---|---|---|---|---|---|---|")
+            for a, b, old, new in pairs:
+                pa, rb = parent[" renamed " + a], result[" renamed " + b]
+                fa, fb = dict(pa[0]), dict(rb[0])
+                worse = [f for f in ("scratch", "vspill", "sspill") if fb[f] > fa[f]]
+                print("| %s | `%s` | `%s` | %s | %d -> %d | %s | %d, %s |" % (a.split(" / ")[0], old, new,
+                                                                       " | ".join("%d -> %d" % (fa[f], fb[f]) for f in ("vgpr", "sgpr", "lds", "scratch", "vspill", "sspill")), len(pa[1]), len(rb[1]),
+                                                                       "identical" if text(a, pa) == text(b, rb) else "differs", len(f64(pa)), "the same by count" if f64(pa) == f64(rb) else "%d in the result" % len(f64(rb))))
+                differ += ["%s -> %s: new %s" % (a, b, ", ".join(worse))] if worse else []
         for fn in CALLS:
             ks = [k for k in parent if k.startswith(fn + " / ")]
-            print("%s.hip.o: %d kernels in the parent, %d in the result, %d instructions; %s" % (fn, len(ks), sum(k.startswith(fn + " / ") for k in result), sum(len(parent[k][1]) for k in ks),
-                                                                                       "identical" if not any(k.startswith(fn + " / ") for k in differ) else "DIFFERENT"))
+            print("%s.hip.o: %d kernels by symbol in the parent, %d in the result, %d instructions; %s; %d renamed" % (
+                fn, len(ks), sum(k.startswith(fn + " / ") for k in result), sum(len(parent[k][1]) for k in ks),
+                "identical" if not any(k.startswith(fn + " / ") for k in differ) else "DIFFERENT", sum(p[0].startswith(fn + " / ") for p in pairs)))
         for k in differ:
             print("DIFFERENT: %s" % k)
         return 1 if differ else 0
     with tempfile.TemporaryDirectory() as tmp:
         for side, root in zip(("parent", "result"), roots):
             path = os.path.join(tmp, side + ".pkl")
-            subprocess.run([sys.executable, os.path.abspath(__file__), "dump", kind, root, path], check=True)
+            subprocess.run([sys.executable, os.path.abspath(__file__), "dump", kind, root, path], check=True, timeout=600)      # (a side that fails or runs out of time ends the comparison)
+            print("%s: the %s's dump is in" % (kind, side), flush=True)
             with open(path, "rb") as f:
                 got.append(pickle.load(f))
     parent, result = got

@@ -375,7 +375,7 @@ def device_flow(Vs, Ms, W0s, H0s, K, T, div, iters, lamW=0.0, lamH=0.0):
         c = (0.5 if div == "euclidean" else 1.0) * maps(b, window(b))[2]
         return (c + lamW * np.abs(Wm[b]).sum()) + lamH * np.abs(Hf[K * off[b]:K * off[b + 1]]).sum()
 
-    for b in range(B):                                                    # wcb_winit
+    for b in range(B):                                                    # nb_winit<CONV, WGT>
         nrm = np.sqrt((Wm[b] ** 2).sum(axis=(0, 2))) / T
         Wm[b] = Wm[b] / nrm[None, :, None]
         spread(b)
@@ -383,7 +383,7 @@ def device_flow(Vs, Ms, W0s, H0s, K, T, div, iters, lamW=0.0, lamH=0.0):
         Hb *= nrm[None, :]
     costs = [[] for _ in range(B)]
     for it in range(iters):
-        for b in range(B):                                                # W-step pass: one slab pair per chunk of 256 columns, then wcb_wupdate
+        for b in range(B):                                                # W-step pass: one slab pair per chunk of 256 columns, then nb_wupdate<CONV, WGT>
             Hwin = window(b)
             A, Bm, _ = maps(b, Hwin)
             Ns, Ps = np.zeros((m, KT)), np.zeros((m, KT))
@@ -400,7 +400,7 @@ def device_flow(Vs, Ms, W0s, H0s, K, T, div, iters, lamW=0.0, lamH=0.0):
         for b in range(B):                                                # H-step pass: Q = WC'*A, P = WC'*B into the K*T x N buffers
             A, Bm, _ = maps(b, window(b))
             Q[:, off[b]:off[b + 1]], P[:, off[b]:off[b + 1]] = WC[b].T @ A, WC[b].T @ Bm
-        for b in range(B):                                                # wcb_hupdate: t ascending, inside the problem Q and P, past its end the kl fill
+        for b in range(B):                                                # nb_hupdate<WGT>: t ascending, inside the problem Q and P, past its end the kl fill
             n = ns[b]
             neg, pos = np.zeros((K, n)), np.zeros((K, n))
             for t in range(T):
